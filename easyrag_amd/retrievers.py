@@ -43,6 +43,9 @@ from .schema import NodeWithScore, QueryBundle, TextNode
 logger = logging.getLogger(__name__)
 
 DEFAULT_SIMILARITY_TOP_K = 2   # llama_index.core.constants.DEFAULT_SIMILARITY_TOP_K
+BM25_DEVICE_MAX_K = 1024       # erh_bm25_topk / erh_hybrid_topk: k_sparse <= 1024
+DENSE_MAX_K = 768              # erh_dense_topk / erh_hybrid_topk: k_dense <= 768
+FUSE_MAX_ITEMS = 2048          # erh_rrf / erh_fusion / erh_hybrid_topk: items of both lists together
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -489,6 +492,9 @@ class HipVectorStore:
         """`filters`: one filter for the whole batch (None, dict, qdrant Filter) or a list with one filter per query."""
         q = _unit_f16(query_embeddings)
         B, k = q.shape[0], int(similarity_top_k)
+        if not 1 <= k <= DENSE_MAX_K:
+            # no exact host fall-back: the chunk matrix lives on the device only
+            raise ValueError(f"dense similarity_top_k must lie in [1, {DENSE_MAX_K}], got {k}")
         dicts = _per_query(filters, B, _filter_to_dict)
         groups = _by_key_set(dicts)
         if len(groups) <= 1:
@@ -665,17 +671,23 @@ class BM25Retriever(_RetrieverBase):
 
     def filter(self, scores: np.ndarray) -> List[NodeWithScore]:
         """Host helper over a caller-supplied score vector (ref retrievers.py:191-210): descending walk
-        (ties by node index), stop at score <= 0, metadata equality filter, first k."""
+        (ties by node index), stop at score <= 0, metadata equality filter, first k.  The length check follows every
+        walked node, rejected ones included, as in the reference: with similarity_top_k == 0 a rejected first node ends
+        the walk with nothing, a kept one leaves the check unmet for the rest of the walk.  A node without a filtered
+        metadata key does not match (the reference raises KeyError there)."""
+        return self._filter_one(scores, self.filter_dict, self._similarity_top_k)
+
+    def _filter_one(self, scores: np.ndarray, filter_dict, top_k: int) -> List[NodeWithScore]:
         scores = np.asarray(scores)
         order = np.lexsort((np.arange(scores.shape[0]), -scores.astype(np.float64)))
         out: List[NodeWithScore] = []
         for ix in order:
             if scores[ix] <= 0:
                 break
-            if self.filter_dict is not None and any(self._nodes[ix].metadata[k] != v for k, v in self.filter_dict.items()):
-                continue
-            out.append(NodeWithScore(node=self._nodes[ix], score=float(scores[ix])))
-            if len(out) == self._similarity_top_k:
+            meta = self._nodes[ix].metadata
+            if filter_dict is None or not any(k not in meta or meta[k] != v for k, v in filter_dict.items()):
+                out.append(NodeWithScore(node=self._nodes[ix], score=float(scores[ix])))
+            if len(out) == top_k:
                 break
         return out
 
@@ -692,6 +704,11 @@ class BM25Retriever(_RetrieverBase):
             return []
         dicts = _per_query(self.filter_dict if filter_dicts is _UNSET else filter_dicts, B, lambda v: dict(v) if v else None)
         tok = [self._query_ids(q) for q in queries]
+        k = self._similarity_top_k
+        if not 1 <= k <= BM25_DEVICE_MAX_K:
+            # outside the fused kernels' range (erh_bm25_topk: 1 <= k <= 1024) the reference's answer is still defined: the
+            # score vector plus the host filter give it exactly
+            return [self._filter_one(self._cast(self.engine.bm25_scores(t, slot=self._slot)), d, k) for t, d in zip(tok, dicts)]
         out: List[List[NodeWithScore]] = [[] for _ in range(B)]
         for g in _by_key_set(dicts):
             qi, qt = queries_to_csr([tok[b] for b in g])
@@ -776,13 +793,16 @@ class HybridRetriever(_RetrieverBase):
     def _fuse(cls, lists, rrf: bool, K: int, topk: int):
         lists = [list(x) for x in lists]
         n_items = sum(len(x) for x in lists)
-        if n_items <= cls.fusion_device_min or n_items > 2048 or len(lists) > 2:
-            return cls._fuse_host(lists, rrf, K, topk)
+        if n_items <= cls.fusion_device_min or n_items > FUSE_MAX_ITEMS or len(lists) > 2 or topk <= 0:
+            return cls._fuse_host(lists, rrf, K, topk)       # (topk <= 0: the reference slices [:0] / [:topk])
         if len(lists) == 1:
             lists.append([])
         items, cid, per_list = _lists_to_device_form(lists)
         if not items:
             return []
+        # the kernel is asked for every fused row (n_items bounds the distinct contents): the reference writes the RRF score
+        # into EVERY fused node, those cut by topk included, and slices afterwards
+        rows = n_items
         da, db = max(len(per_list[0]), 1), max(len(per_list[1]), 1)
         ia = np.full((1, da), -1, np.int32)
         ib = np.full((1, db), -1, np.int32)
@@ -794,20 +814,20 @@ class HybridRetriever(_RetrieverBase):
             eng = _fusion_engine()
             eng.set_doc_meta(len(items), cid, None)
             if rrf:
-                ids, sc, ln = eng.rrf(ia, la, ib, lb, K=K, topk=topk)
+                ids, sc, ln = eng.rrf(ia, la, ib, lb, K=K, topk=rows)
             else:
                 sa = np.zeros((1, da), np.float64)
                 sb = np.zeros((1, db), np.float64)
                 sa[0, :la[0]] = [items[i].score for i in per_list[0]]
                 sb[0, :lb[0]] = [items[i].score for i in per_list[1]]
-                ids, sc, ln = eng.fusion(ia, sa, la, ib, sb, lb, topk=topk)
+                ids, sc, ln = eng.fusion(ia, sa, la, ib, sb, lb, topk=rows)
         out = []
         for i, s in zip(ids[0, :ln[0]], sc[0, :ln[0]]):
             node = items[i]
             if rrf:
                 node.score = float(s)        # the reference overwrites the node's score with the RRF score
             out.append(node)
-        return out
+        return out[:topk]
 
     @classmethod
     def fusion(cls, list_of_list_ranks_system, topk: int = 256):
@@ -822,6 +842,11 @@ class HybridRetriever(_RetrieverBase):
         vs = getattr(self.dense_retriever, "_vector_store", None)
         return (isinstance(vs, HipVectorStore) and vs.engine is self.sparse_retriever.engine
                 and len(vs.nodes) == len(self.sparse_retriever._nodes))
+
+    def _fused_sizes(self) -> bool:
+        """topk / k_sparse / k_dense within what erh_hybrid_topk accepts."""
+        ks, kd = self.sparse_retriever._similarity_top_k, self.dense_retriever._similarity_top_k
+        return self.topk >= 1 and 1 <= ks <= BM25_DEVICE_MAX_K and 1 <= kd <= DENSE_MAX_K and ks + kd <= FUSE_MAX_ITEMS
 
     def _retrieve(self, query_bundle: QueryBundle) -> List[NodeWithScore]:
         """The reference's sync path (retrievers.py:293-305, marked unmaintained there): both routes with whatever
@@ -866,7 +891,8 @@ class HybridRetriever(_RetrieverBase):
         d_sparse = _per_query(fs, B, lambda v: dict(v) if v else None)
         d_dense = _per_query(fdn, B, _filter_to_dict)
         key_sets = {tuple(sorted(fd)) for fd in d_sparse + d_dense if fd}
-        if not self._fused_possible() or len(key_sets) > 1:
+        if not self._fused_possible() or len(key_sets) > 1 or not self._fused_sizes():
+            # (outside erh_hybrid_topk's sizes the routes run on their own: each one falls back or names its limit)
             sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs), de.retrieve_batch(queries, filters=fdn)
             return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
         # both routes share one engine: BM25 -> dense -> RRF([sparse, dense]) in a single device pipeline, one class column
