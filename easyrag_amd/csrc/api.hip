@@ -62,7 +62,8 @@ int erh_destroy(erh_handle *h) {
                       &h->o_ids, &h->o_sc, &h->o_len, &h->qpack, &h->part_sc, &h->part_ids, &h->part_len,
                       &h->hy_sids, &h->hy_ssc, &h->hy_slen, &h->hy_dids, &h->hy_dsc, &h->hy_dlen,
                       &h->fa_ids, &h->fa_sc, &h->fa_len, &h->fb_ids, &h->fb_sc, &h->fb_len,
-                      &h->scores_tmp, &h->scores_wide, &h->dbg, &h->dstats, &h->dir_pos, &h->seed_need, &h->bad, &h->ex_ws, &h->bm_redo, &h->fin_ws, &h->dir_rng, &h->Xb, &h->blk_tmp, &h->blk_ids, &h->r_q, &h->r_ids, &h->r_sc, &h->r_len, &h->r_flags, &h->r_tab, &h->r_q16, &h->bm_fin_ids, &h->bm_fin_cnt};
+                      &h->scores_tmp, &h->scores_wide, &h->dbg, &h->dstats, &h->dir_pos, &h->seed_need, &h->bad, &h->ex_ws, &h->bm_redo, &h->fin_ws, &h->dir_rng, &h->Xb, &h->blk_tmp, &h->blk_ids, &h->r_q, &h->r_ids, &h->r_sc, &h->r_len, &h->r_flags, &h->r_tab, &h->r_q16, &h->bm_fin_ids, &h->bm_fin_cnt,
+                      &h->s_tab, &h->s_q, &h->s_ids, &h->s_sc, &h->s_len};
     for (DevBuf *b : bufs) b->release();
     if (h->r_flags_host) (void)hipHostFree(h->r_flags_host);
     for (auto &b : h->bm) b.release();
@@ -186,8 +187,9 @@ int erh_reset_kernel_time(erh_handle *h) {
 
 int erh_dense_check(erh_handle *h, void *stream) {
     if (!h) return ERH_ERR_INVALID;
-    if (!h->flags.p || (!h->last.valid && !h->routed.done)) return ERH_OK;           // no dense route has run on this handle
+    if (!h->sets.on && (!h->flags.p || (!h->last.valid && !h->routed.done))) return ERH_OK;   // no dense route has run on this handle
     HIPCHK(h, hipSetDevice(h->device));
+    if (h->sets.on) return dense_sets_check(h, (hipStream_t)stream);
     return dense_check_flags(h, (hipStream_t)stream);
 }
 
@@ -845,10 +847,154 @@ int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, i
         d_ids = h->o_ids.as<int32_t>(); d_sc = h->o_sc.as<double>(); d_len = h->o_len.as<int32_t>();
     }
     h->stats.dense_calls += 1;
+    h->sets.on = false;
     rc = dense_topk_routed(h, qd, q_dtype, normalize_q, B, k, filter_dir, filt, mode, d_ids, d_sc, d_len, st);
     if (rc != ERH_OK) return rc;
     if (!out_is_device) {
         rc = dense_check_flags(h, st);                  // (may run further exhaustive rounds before the copy)
+        if (rc != ERH_OK) return rc;
+        return copy_out(h, B, k, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
+    }
+    return ERH_OK;
+}
+
+// Set filters: every (query, allowed class) pair is a sub-query of ONE ordinary class-column batch through dense_topk_routed (in chunks of
+// kSetsChunk sub-queries when the batch is larger: every chunk but the last is checked before the next one reuses the work space), then
+// one merge launch (dense_sets.hip) builds each query's list from its sub-lists.  An unfiltered query ({-1}) is one sub-query without a
+// class, an empty set none.  erh_dense_check -> dense_sets_check: the sub-queries' flag words, and the merge again if they changed a list.
+static constexpr int kSetsChunk = 8192;
+
+}  // extern "C"
+
+int dense_sets_check(erh_handle *h, hipStream_t st) {
+    erh_handle::DenseSets &S = h->sets;
+    int rc = ERH_OK;
+    h->dense_corrected = false;
+    if (S.n_sub > 0) {
+        rc = dense_check_flags(h, st);
+        if (rc != ERH_OK) return rc;
+        h->diag_maxerr = std::max(h->diag_maxerr, S.acc_maxerr);
+        h->diag_uncert += S.acc_uncert;
+        h->diag_exhaustive += S.acc_exhaustive;
+        S.acc_maxerr = 0; S.acc_uncert = 0; S.acc_exhaustive = 0;
+    } else {
+        h->diag_maxerr = 0; h->diag_uncert = 0; h->diag_exhaustive = 0;
+    }
+    if (h->dense_corrected) {                          // a sub-list changed after the merge: merge all of them again
+        HIPCHK(h, erh::launch_dense_set_merge(h->s_ids.as<int32_t>(), h->s_sc.as<double>(), h->s_len.as<int32_t>(), h->s_tab.as<int32_t>(),
+                                              S.B, S.k, S.d_ids, S.d_sc, S.d_len, st));
+        h->dense_corrected = false;
+    }
+    HIPCHK(h, hipStreamSynchronize(st));
+    return ERH_OK;
+}
+
+extern "C" {
+
+int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
+                        int B, int k, const int32_t *set_ptr, const int16_t *set_cls, int mode,
+                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
+    if (!h) return ERH_ERR_INVALID;
+    if (!h->X.p || h->N <= 0) return h->fail(ERH_ERR_STATE, "erh_dense_topk_sets before erh_set_dense");
+    if (!q || !out_ids || !out_scores || !out_len || !set_ptr || B <= 0 || k <= 0)
+        return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: null pointer or non-positive B/k");
+    if (q_dtype != ERH_F16 && q_dtype != ERH_F32) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: q_dtype");
+    if (mode != ERH_DENSE_EXACT && mode != ERH_DENSE_FAST) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: mode");
+    if (k > 768) return h->fail(ERH_ERR_UNSUPPORTED, "erh_dense_topk_sets: k > 768");
+    // the CSR: monotone, classes >= 0 (32767 = matches nothing) and distinct within a set, or the set {-1} alone
+    if (set_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: set_ptr[0] != 0");
+    for (int b = 0; b < B; ++b)
+        if (set_ptr[b + 1] < set_ptr[b]) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: set_ptr not monotone");
+    if (set_ptr[B] > 0 && !set_cls) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: null set_cls");
+    bool any_class = false;
+    {
+        std::vector<int16_t> tmp;
+        for (int b = 0; b < B; ++b) {
+            const int m = set_ptr[b + 1] - set_ptr[b];
+            const int16_t *c = set_cls + set_ptr[b];
+            if (m == 1 && c[0] == -1) continue;
+            tmp.assign(c, c + m);
+            std::sort(tmp.begin(), tmp.end());
+            for (int i = 0; i < m; ++i) {
+                if (tmp[i] < 0) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: negative class (only the set {-1} means unfiltered)");
+                if (i && tmp[i] == tmp[i - 1]) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: a class twice in one set");
+            }
+            any_class = any_class || m > 0;
+        }
+    }
+    if (any_class && (!h->has_dir || h->Nmeta < h->N))
+        return h->fail(ERH_ERR_STATE, "erh_dense_topk_sets: set filter given but erh_set_doc_meta(dir_id) not set for all documents");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    // the sub-query batch: a class that no document carries (32767, or beyond the classes erh_set_doc_meta saw) contributes nothing and
+    // gets no sub-query; an unfiltered query one without a class
+    const int nc = (int)h->dir_cnt_h.size();
+    std::vector<int32_t> sub_ptr((size_t)B + 1, 0), src;
+    std::vector<int16_t> cls;
+    for (int b = 0; b < B; ++b) {
+        const int m = set_ptr[b + 1] - set_ptr[b];
+        const int16_t *c = set_cls ? set_cls + set_ptr[b] : nullptr;
+        if (m == 1 && c[0] == -1) { src.push_back(b); cls.push_back(-1); }
+        else
+            for (int i = 0; i < m; ++i)
+                if (c[i] < nc && h->dir_cnt_h[c[i]] > 0) { src.push_back(b); cls.push_back(c[i]); }
+        sub_ptr[(size_t)b + 1] = (int32_t)src.size();
+    }
+    const int n_sub = (int)src.size();
+    const size_t off_src = ((size_t)B + 1) * 4, off_cls = off_src + (size_t)n_sub * 4;
+    {
+        std::vector<char> tab(off_cls + (size_t)n_sub * 2);
+        memcpy(tab.data(), sub_ptr.data(), off_src);
+        if (n_sub) { memcpy(tab.data() + off_src, src.data(), (size_t)n_sub * 4); memcpy(tab.data() + off_cls, cls.data(), (size_t)n_sub * 2); }
+        HIPCHK(h, h->s_tab.ensure(tab.size()));
+        HIPCHK(h, hipMemcpyAsync(h->s_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipStreamSynchronize(st));           // (`tab` is pageable memory of this scope)
+    }
+    const int32_t *d_ptr = h->s_tab.as<int32_t>();
+    const int32_t *d_src = reinterpret_cast<const int32_t *>(h->s_tab.as<char>() + off_src);
+    const int16_t *d_cls = reinterpret_cast<const int16_t *>(h->s_tab.as<char>() + off_cls);
+    int32_t *d_ids = out_ids; double *d_sc = out_scores; int32_t *d_len = out_len;
+    if (!out_is_device) {
+        HIPCHK(h, h->o_ids.ensure((size_t)B * k * 4));
+        HIPCHK(h, h->o_sc.ensure((size_t)B * k * 8));
+        HIPCHK(h, h->o_len.ensure((size_t)B * 4));
+        d_ids = h->o_ids.as<int32_t>(); d_sc = h->o_sc.as<double>(); d_len = h->o_len.as<int32_t>();
+    }
+    h->stats.dense_calls += 1;
+    erh_handle::DenseSets &S = h->sets;
+    S = erh_handle::DenseSets();
+    S.B = B; S.k = k; S.n_sub = n_sub; S.d_ids = d_ids; S.d_sc = d_sc; S.d_len = d_len;
+    if (n_sub > 0) {
+        const void *qd = nullptr;
+        int rc = stage_query_block(h, q, q_dtype, q_is_device, B, st, &qd);
+        if (rc != ERH_OK) return rc;
+        const size_t row_bytes = (size_t)h->d * (q_dtype == ERH_F16 ? 2 : 4);
+        HIPCHK(h, h->s_q.ensure((size_t)n_sub * row_bytes));
+        HIPCHK(h, h->s_ids.ensure((size_t)n_sub * k * 4));
+        HIPCHK(h, h->s_sc.ensure((size_t)n_sub * k * 8));
+        HIPCHK(h, h->s_len.ensure((size_t)n_sub * 4));
+        HIPCHK(h, erh::launch_gather_query_rows(qd, d_src, n_sub, (int)row_bytes, h->s_q.p, st));
+        for (int c0 = 0; c0 < n_sub; c0 += kSetsChunk) {
+            const int nb = std::min(kSetsChunk, n_sub - c0);
+            if (c0 > 0) {                              // the previous chunk must be final before this one reuses the work space
+                rc = dense_check_flags(h, st);
+                if (rc != ERH_OK) return rc;
+                S.acc_maxerr = std::max(S.acc_maxerr, h->diag_maxerr); S.acc_uncert += h->diag_uncert; S.acc_exhaustive += h->diag_exhaustive;
+            }
+            bool filtered = false;
+            for (int i = 0; i < nb; ++i) filtered = filtered || cls[(size_t)c0 + i] >= 0;
+            rc = dense_topk_routed(h, h->s_q.as<char>() + (size_t)c0 * row_bytes, q_dtype, normalize_q, nb, k,
+                                   filtered ? cls.data() + c0 : nullptr, filtered ? d_cls + c0 : nullptr, mode,
+                                   h->s_ids.as<int32_t>() + (size_t)c0 * k, h->s_sc.as<double>() + (size_t)c0 * k,
+                                   h->s_len.as<int32_t>() + c0, st);
+            if (rc != ERH_OK) return rc;
+        }
+    }
+    HIPCHK(h, erh::launch_dense_set_merge(h->s_ids.as<int32_t>(), h->s_sc.as<double>(), h->s_len.as<int32_t>(), d_ptr, B, k,
+                                          d_ids, d_sc, d_len, st));
+    S.on = true;
+    if (!out_is_device) {
+        int rc = dense_sets_check(h, st);
         if (rc != ERH_OK) return rc;
         return copy_out(h, B, k, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
     }
@@ -1017,6 +1163,7 @@ int erh_hybrid_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, 
     // inputs were staged there) and joins it again in front of the fusion; whatever the dense pipeline leaves idle --
     // the under-filled seed grid, the selection kernels, the tail of the persistent scan -- the other route can use.
     h->stats.hybrid_calls += 1;
+    h->sets.on = false;
     hipStream_t st_sparse = st;
     const int ov = h->opt_hybrid_overlap >= 0 ? h->opt_hybrid_overlap : (B <= 256 ? 1 : 0);
     if (ov) {

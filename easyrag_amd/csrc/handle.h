@@ -185,6 +185,16 @@ struct erh_handle {
     std::vector<int16_t> r_filt_host;
     std::vector<uint32_t> r_bad_host;
     std::vector<char> r_tab_host;
+    // erh_dense_topk_sets: its sub-query batch (one row per (query, allowed class)) and where the merged lists go.  The sub-lists stay in s_ids /
+    // s_sc / s_len until erh_dense_check has read the flag words: a sub-query answered by the exhaustive path there is merged again.
+    struct DenseSets {
+        bool on = false;                     // the last dense call was erh_dense_topk_sets: erh_dense_check finishes it (dense_sets_check)
+        int B = 0, k = 0, n_sub = 0;
+        int32_t *d_ids = nullptr; double *d_sc = nullptr; int32_t *d_len = nullptr;
+        double acc_maxerr = 0; int32_t acc_uncert = 0, acc_exhaustive = 0;   // diag of the chunks checked before the last one
+    } sets;
+    DevBuf s_tab, s_q, s_ids, s_sc, s_len;   // s_tab: sub_ptr int32[B+1] | source row int32[n_sub] | class int16[n_sub], one upload
+    bool dense_corrected = false;            // dense_check_flags changed result rows (exhaustive rounds or a group run again)
     DevBuf dir_rng;                          // {first document, last + 1} of every dir class (erh_set_doc_meta): a filtered BM25 query walks those tiles only
     int dir_rng_n = 0;
     int opt_bm25_dir_range = 1;
@@ -367,6 +377,7 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
 int dense_topk_routed(erh_handle *h, const void *q_dev, int q_dtype, int normalize_q, int B, int k, const int16_t *filter_host,
                       const int16_t *filter_dev, int mode, int32_t *d_ids, double *d_sc, int32_t *d_len, hipStream_t st);
 int dense_check_flags(erh_handle *h, hipStream_t st);
+int dense_sets_check(erh_handle *h, hipStream_t st);   // erh_dense_check after erh_dense_topk_sets (api.hip)
 int bm25_topk_dev(erh_handle *h, const int32_t *qptr_dev, const int32_t *qtok_dev, int B, int k,
                   const int16_t *filter_dev, int32_t *d_ids, double *d_sc, int32_t *d_len, double postings_bytes,
                   int max_qlen, hipStream_t st);

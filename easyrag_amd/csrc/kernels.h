@@ -162,6 +162,10 @@ hipError_t launch_gather_query_rows(const void *q, const int32_t *idx, int n, in
 hipError_t launch_scatter_topk_rows(const int32_t *ids, const double *sc, const int32_t *len, const int32_t *idx, int n, int k,
                                     int32_t id_offset, const int32_t *id_map /* null: id + id_offset; else id_map[id_offset + id] */,
                                     int32_t *out_ids, double *out_sc, int32_t *out_len, hipStream_t st);
+// set filters (dense_sets.hip): out row b = the canonical top k of the union of the sub-lists sub_ptr[b] .. sub_ptr[b + 1] of [rows x k]
+// (each canonical, disjoint row sets); k <= 768; no sub-list: length 0
+hipError_t launch_dense_set_merge(const int32_t *sub_ids, const double *sub_sc, const int32_t *sub_len, const int32_t *sub_ptr, int B, int k,
+                                  int32_t *out_ids, double *out_sc, int32_t *out_len, hipStream_t st);
 // Exhaustive path for the queries flagged in bad[] (select.hip): exact fp64 scores of every chunk + streaming top-k.
 int dense_exhaustive_max();
 size_t dense_exhaustive_bytes(int64_t N);

@@ -452,6 +452,7 @@ int dense_check_flags(erh_handle *h, hipStream_t st) {
                                       saved.k, cid, saved.B, saved.K, saved.topk, saved.f_ids, saved.f_sc, saved.f_len, st));
         }
         if (redone) HIPCHK(h, hipStreamSynchronize(st));
+        if (redone) h->dense_corrected = true;
         h->last = erh_handle::LastDense();
         R.done = true;
         h->diag_maxerr = maxerr; h->diag_uncert = uncert; h->diag_exhaustive = exhaustive;
@@ -462,6 +463,7 @@ int dense_check_flags(erh_handle *h, hipStream_t st) {
     HIPCHK(h, hipMemcpyAsync(f, h->flags.p, sizeof f, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     if (f[0] && h->last.valid) {
+        h->dense_corrected = true;
         const int total = (int)f[3], per = erh::dense_exhaustive_max();
         const erh_handle::LastDense &L = h->last;
         for (int skip = 0; skip < total; skip += per)          // (the call enqueued the count only: every answering round runs here)

@@ -314,6 +314,31 @@ class RetrievalEngine:
                                              1 if device_out else 0, self._stream(stream)))
         return ids, sc, ln
 
+    @staticmethod
+    def sets_to_csr(sets, B: int) -> Tuple[np.ndarray, np.ndarray]:
+        """One class set per query (a sequence of class ids, or None = unfiltered) -> (set_ptr int32[B+1], set_cls int16[...])."""
+        if len(sets) != B:
+            raise ValueError("sets must have one entry per query")
+        rows = [[-1] if s is None else [int(c) for c in s] for s in sets]
+        ptr = np.zeros(B + 1, np.int32)
+        np.cumsum([len(r) for r in rows], out=ptr[1:])
+        cls = np.fromiter((c for r in rows for c in r), dtype=np.int64, count=int(ptr[-1]))
+        if cls.size and (cls.min() < -1 or cls.max() > 32767):
+            raise ValueError("class ids must lie in [-1, 32767]")
+        return ptr, cls.astype(np.int16)
+
+    def dense_topk_sets(self, q, k: int, sets, mode: int = _lib.ERH_DENSE_EXACT, normalize_q: bool = False,
+                        device_out: bool = False, stream=None):
+        """Dense top-k where query b may see the rows whose class is in sets[b] (erh_dense_topk_sets): a sequence of class ids,
+        None for unfiltered; an empty sequence returns nothing.  device_out: results are final after dense_check()."""
+        q, dt, is_dev, B = self._q_desc(q)
+        ptr, cls = self.sets_to_csr(sets, B)
+        ids, sc, ln = self._outs(B, k, device_out)
+        self._check(self._lib.erh_dense_topk_sets(self._h, _ptr(q), dt, is_dev, 1 if normalize_q else 0, B, int(k),
+                                                  _ptr(ptr), _ptr(cls), int(mode), _ptr(ids), _ptr(sc), _ptr(ln),
+                                                  1 if device_out else 0, self._stream(stream)))
+        return ids, sc, ln
+
     def bm25_topk(self, q_indptr, q_tok, k: int, filter_dir=None, device_out: bool = False, stream=None,
                   slot: Optional[int] = None):
         self._select(slot)
@@ -351,6 +376,18 @@ class RetrievalEngine:
         ids, sc, ln = self._outs(B, topk, False)
         self._check(self._lib.erh_rrf(self._h, _ptr(ids_a), _ptr(la), ids_a.shape[1], _ptr(ids_b), _ptr(lb),
                                       ids_b.shape[1], B, int(K), int(topk), _ptr(ids), _ptr(sc), _ptr(ln), 0, 0))
+        return ids, sc, ln
+
+    def rrf_device(self, ids_a, len_a, ids_b, len_b, K: int = 60, topk: int = 256, stream=None):
+        """erh_rrf over DEVICE lists (torch tensors, e.g. the device outputs of bm25_topk / dense_topk_sets after dense_check):
+        the fused [B, topk] lists stay on the device; complete after sync()."""
+        B = int(ids_a.shape[0])
+        if int(ids_b.shape[0]) != B:
+            raise ValueError("the two lists must have one row per query each")
+        ids, sc, ln = self._outs(B, topk, True)
+        self._check(self._lib.erh_rrf(self._h, _ptr(ids_a), _ptr(len_a), int(ids_a.shape[1]), _ptr(ids_b), _ptr(len_b),
+                                      int(ids_b.shape[1]), B, int(K), int(topk), _ptr(ids), _ptr(sc), _ptr(ln), 1,
+                                      self._stream(stream)))
         return ids, sc, ln
 
     def fusion(self, ids_a, sc_a, len_a, ids_b, sc_b, len_b, topk: int = 256):

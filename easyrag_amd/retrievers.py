@@ -167,20 +167,168 @@ class _MetaClasses:
         return self.values.get(v, 32767)          # 32767 matches no document
 
 
-def _filter_to_dict(filters) -> Optional[Dict[str, Any]]:
-    """Accept None, a {key: value} dict, or a qdrant-style Filter(must=[FieldCondition(key, match=MatchValue(value))])
-    (what build_qdrant_filters returns, ref ingestion.py:207-216)."""
+# ---------------------------------------------------------------------------------------------------
+# Qdrant payload filters beyond the pipeline's equality shape.  The reference's QdrantRetriever hands `filters` to Qdrant unchanged
+# (ref retrievers.py:44-47), so any Qdrant filter works there.  Here a filter is compiled (duck typing on Qdrant's attribute names:
+# qdrant_client's models and stand-ins with the same fields both work) into a hashable tree, evaluated on the host once per distinct
+# value tuple of the class column over the keys it mentions, and reaches the device as the SET of classes a query may see.  Values
+# compare as Python does (1 == 1.0 == True: the class column keys its classes by them), and a metadata value None counts as an absent
+# key (the class column does not tell the two apart either).  Grammar (restated from Qdrant's documentation,
+# unpinned like the rest of the third-party surface): Filter(must, should, must_not) with nesting, FieldCondition(key, match=MatchValue
+# / MatchAny / MatchExcept) and FieldCondition(key, range=Range(gt, gte, lt, lte)); anything else raises TypeError.
+_FILTER_VALUE_TYPES = (str, int, float, bool)
+
+
+def _clause(v) -> list:
+    if v is None:
+        return []
+    return list(v) if isinstance(v, (list, tuple)) else [v]
+
+
+def _value(v, where: str):
+    if isinstance(v, np.generic):
+        v = v.item()
+    if not isinstance(v, _FILTER_VALUE_TYPES):
+        raise TypeError(f"unsupported filter value {v!r} in {where}")
+    return v
+
+
+def _bound(v, where: str):
+    if v is None:
+        return None
+    if isinstance(v, np.generic):
+        v = v.item()
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise TypeError(f"unsupported Range bound {v!r} in {where} (numbers only)")
+    return v
+
+
+def _compile_condition(c, keys: set):
+    """One condition -> a hashable tree node; `keys` collects the metadata keys it mentions."""
+    name = type(c).__name__
+    if hasattr(c, "key"):                                          # FieldCondition
+        key = c.key
+        if not isinstance(key, str) or "." in key or "[" in key:
+            raise TypeError(f"unsupported FieldCondition key {key!r} (nested / array key paths)")
+        for attr in ("geo_bounding_box", "geo_radius", "geo_polygon", "values_count", "is_empty", "is_null"):
+            if getattr(c, attr, None) is not None:
+                raise TypeError(f"unsupported FieldCondition element {attr} on key {key!r}")
+        match, rng = getattr(c, "match", None), getattr(c, "range", None)
+        if (match is None) == (rng is None):
+            raise TypeError(f"unsupported FieldCondition on key {key!r}: exactly one of match / range is supported")
+        keys.add(key)
+        if rng is not None:
+            where = f"Range on {key!r}"
+            for attr in ("gt", "gte", "lt", "lte"):
+                if not hasattr(rng, attr):
+                    raise TypeError(f"unsupported range object {type(rng).__name__} on key {key!r}")
+            return ("range", key, _bound(rng.gt, where), _bound(rng.gte, where), _bound(rng.lt, where), _bound(rng.lte, where))
+        mname = type(match).__name__
+        if hasattr(match, "any"):                                  # MatchAny
+            return ("any", key, tuple(sorted({_value(v, f"{mname} on {key!r}") for v in _clause(match.any)}, key=repr)))
+        exc = getattr(match, "except_", None)
+        if exc is None:
+            exc = getattr(match, "except", None)
+        if exc is not None or hasattr(match, "except_"):           # MatchExcept (attribute `except_`, alias `except`)
+            return ("except", key, tuple(sorted({_value(v, f"{mname} on {key!r}") for v in _clause(exc)}, key=repr)))
+        if hasattr(match, "value") and not hasattr(match, "text"):  # MatchValue
+            return ("eq", key, _value(match.value, f"{mname} on {key!r}"))
+        raise TypeError(f"unsupported match {mname} on key {key!r} (MatchValue / MatchAny / MatchExcept only)")
+    if any(hasattr(c, a) for a in ("must", "should", "must_not")):  # Filter (nesting)
+        if getattr(c, "min_should", None) is not None:
+            raise TypeError("unsupported Filter element min_should")
+        return ("filter", tuple(_compile_condition(x, keys) for x in _clause(getattr(c, "must", None))),
+                tuple(_compile_condition(x, keys) for x in _clause(getattr(c, "should", None))),
+                tuple(_compile_condition(x, keys) for x in _clause(getattr(c, "must_not", None))))
+    raise TypeError(f"unsupported filter condition {name}: {c!r}")
+
+
+def _holds(node, meta: Dict[str, Any]) -> bool:
+    """Evaluate a compiled node on one row's metadata ({key: value}, absent keys missing)."""
+    op = node[0]
+    if op == "filter":
+        _, must, should, must_not = node
+        return (all(_holds(x, meta) for x in must) and (not should or any(_holds(x, meta) for x in should))
+                and not any(_holds(x, meta) for x in must_not))
+    key = node[1]
+    if key not in meta:
+        return False                                               # a row without the key fails every condition on it
+    v = meta[key]
+    if op == "range":
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            return False
+        gt, gte, lt, lte = node[2:]
+        return ((gt is None or v > gt) and (gte is None or v >= gte) and (lt is None or v < lt) and (lte is None or v <= lte))
+    if op == "eq":
+        return v == node[2]
+    hit = any(v == w for w in node[2])
+    return hit if op == "any" else not hit
+
+
+class _SetFilter:
+    """A compiled filter that is not the equality shape: its tree and the metadata keys it mentions (its key set)."""
+
+    __slots__ = ("node", "keys")
+
+    def __init__(self, node, keys: Sequence[str]):
+        self.node = node
+        self.keys = tuple(sorted(keys))
+
+    def __iter__(self):                        # iterates like a dict's keys: _by_key_set / key-set checks treat both alike
+        return iter(self.keys)
+
+    def __bool__(self):
+        return True
+
+
+_MATCH_NOTHING = _SetFilter(("filter", (), (), (("filter", (), (), ()),)), ())   # must_not=[empty Filter]: no row
+
+
+def _filter_spec(filters):
+    """None / {key: value} dict / Qdrant-style Filter -> None (unfiltered), a dict (the equality shape: exactly today's class column),
+    or a _SetFilter.  Unsupported elements raise TypeError here, before any engine call."""
     if filters is None:
         return None
     if isinstance(filters, dict):
         return dict(filters) or None
-    must = getattr(filters, "must", None)
-    if must:
-        out = {}
-        for cond in must:
-            out[getattr(cond, "key")] = getattr(getattr(cond, "match"), "value")
-        return out or None
-    raise TypeError(f"unsupported filter object: {filters!r}")
+    keys: set = set()
+    node = _compile_condition(filters, keys)
+    if node[0] != "filter":
+        raise TypeError(f"unsupported filter object: {filters!r} (a Filter is expected at the top level)")
+    _, must, should, must_not = node
+    if not must and not should and not must_not:
+        return None                                                # an empty Filter matches every row
+    if (must and not should and not must_not and all(x[0] == "eq" for x in must)
+            and len({x[1] for x in must}) == len(must)):
+        return {x[1]: x[2] for x in must}                          # Filter(must=[MatchValue, ...]): the pipeline's shape
+    if not keys:                                                   # nested empty filters only: a constant
+        return None if _holds(node, {}) else _MATCH_NOTHING
+    return _SetFilter(node, keys)
+
+
+def _filter_to_dict(filters) -> Optional[Dict[str, Any]]:
+    """The equality shape only (None, a {key: value} dict, Filter(must=[FieldCondition(key, match=MatchValue(value))]) as
+    build_qdrant_filters returns it, ref ingestion.py:207-216); other filters raise TypeError.  The retrievers use _filter_spec."""
+    spec = _filter_spec(filters)
+    if isinstance(spec, _SetFilter):
+        raise TypeError(f"not an equality filter: {filters!r}")
+    return spec
+
+
+def _spec_cache() -> Callable[[Any], Any]:
+    """_filter_spec with one compilation per distinct filter object of a batch (a per-query list repeats the same few)."""
+    seen: Dict[int, tuple] = {}
+
+    def spec(v):
+        hit = seen.get(id(v))
+        if hit is None:
+            hit = seen[id(v)] = (v, _filter_spec(v))     # (v is held, so its id stays its own for the batch)
+        return hit[1]
+    return spec
+
+
+def _spec_keys(spec) -> tuple:
+    return tuple(sorted(spec)) if spec else ()
 
 
 class _FilteredCorpus:
@@ -214,6 +362,46 @@ class _FilteredCorpus:
             self._classes = cache[keys]
             self._push_meta()
         return self._classes.class_of(filter_dict)
+
+    def _use_keys(self, keys: tuple) -> "_MetaClasses":
+        if self._classes is None or self._classes.keys != keys:
+            cache = self.__dict__.setdefault("_class_tables", {})
+            if keys not in cache:
+                cache[keys] = _MetaClasses(self.nodes, keys)
+            self._classes = cache[keys]
+            self._push_meta()
+        return self._classes
+
+    def class_set(self, spec: "_SetFilter") -> Optional[List[int]]:
+        """Classes (of the column over spec.keys) whose value tuple satisfies the filter, ascending; None = every class.  The
+        evaluation is cached per class table and compiled filter: the reference's loop sends the same few filters over and over."""
+        if not spec.keys:
+            return None if _holds(spec.node, {}) else []
+        table = self._use_keys(spec.keys)
+        cache = table.__dict__.setdefault("_set_cache", {})
+        hit = cache.get(spec.node)
+        if hit is None:
+            allowed = [j for vals, j in table.values.items()
+                       if _holds(spec.node, {k: v for k, v in zip(table.keys, vals) if v is not None})]
+            hit = ("all",) if len(allowed) == len(table.values) else tuple(sorted(allowed))
+            if len(cache) >= 4096:
+                cache.clear()
+            cache[spec.node] = hit
+        return None if hit == ("all",) else list(hit)
+
+    def plan(self, specs: Sequence[Any]) -> List[Any]:
+        """Per query of one key-set group: -1 (unfiltered), a class id (today's column path), or a list of >= 2 class ids; [] = no
+        row can match (the query returns nothing without a scan).  Dicts keep today's classes (32767 = matches nothing)."""
+        out: List[Any] = []
+        for sp in specs:
+            if not sp:
+                out.append(-1)
+            elif isinstance(sp, dict):
+                out.append(self.filter_class(sp))
+            else:
+                cs = self.class_set(sp)
+                out.append(-1 if cs is None else (cs[0] if len(cs) == 1 else cs))
+        return out
 
     def filter_column(self, filter_dicts: Sequence[Optional[Dict[str, Any]]]) -> Optional[np.ndarray]:
         """int16[B] class column for a batch whose queries carry their OWN filters (None / {} = unfiltered: -1), or None
@@ -253,8 +441,9 @@ def _by_key_set(dicts: Sequence[Optional[Dict[str, Any]]]) -> List[List[int]]:
     groups: Dict[tuple, List[int]] = {}
     free: List[int] = []
     for b, fd in enumerate(dicts):
-        if fd:
-            groups.setdefault(tuple(sorted(fd)), []).append(b)
+        keys = _spec_keys(fd)          # (a set filter's key set = every key it mentions; a constant one needs no column)
+        if keys:
+            groups.setdefault(keys, []).append(b)
         else:
             free.append(b)
     out = list(groups.values())
@@ -495,14 +684,33 @@ class HipVectorStore:
         if not 1 <= k <= DENSE_MAX_K:
             # no exact host fall-back: the chunk matrix lives on the device only
             raise ValueError(f"dense similarity_top_k must lie in [1, {DENSE_MAX_K}], got {k}")
-        dicts = _per_query(filters, B, _filter_to_dict)
+        dicts = _per_query(filters, B, _spec_cache())
         groups = _by_key_set(dicts)
-        if len(groups) <= 1:
+        has_sets = any(isinstance(sp, _SetFilter) for sp in dicts)
+        if len(groups) <= 1 and not has_sets:
             return self.engine.dense_topk(q, k, filter_dir=self.corpus.filter_column(dicts), mode=mode)
         ids, sc, ln = np.full((B, k), -1, np.int32), np.zeros((B, k), np.float64), np.zeros(B, np.int32)
         for g in groups:                              # filters over different metadata keys: one device column at a time
-            gi, gs, gl = self.engine.dense_topk(q[g], k, filter_dir=self.corpus.filter_column([dicts[b] for b in g]), mode=mode)
+            if has_sets:
+                gi, gs, gl = self._query_planned(q[g], k, self.corpus.plan([dicts[b] for b in g]), mode)
+            else:
+                gi, gs, gl = self.engine.dense_topk(q[g], k, filter_dir=self.corpus.filter_column([dicts[b] for b in g]), mode=mode)
             ids[g], sc[g], ln[g] = gi, gs, gl
+        return ids, sc, ln
+
+    def _query_planned(self, q, k: int, plan: List[Any], mode: int):
+        """One key-set group after corpus.plan: queries whose filter matches no row get nothing (no scan); a group without a
+        set of two or more classes is today's class-column call, any other erh_dense_topk_sets."""
+        B = len(plan)
+        live = [b for b in range(B) if not (isinstance(plan[b], list) and not plan[b])]
+        if any(isinstance(c, list) and len(c) > 1 for c in plan):
+            return self.engine.dense_topk_sets(q, k, [None if c == -1 else (c if isinstance(c, list) else [c]) for c in plan],
+                                               mode=mode)
+        ids, sc, ln = np.full((B, k), -1, np.int32), np.zeros((B, k), np.float64), np.zeros(B, np.int32)
+        if live:
+            col = np.asarray([plan[b] for b in live], np.int16)
+            ids[live], sc[live], ln[live] = self.engine.dense_topk(q[live], k, filter_dir=col if np.any(col >= 0) else None,
+                                                                   mode=mode)
         return ids, sc, ln
 
     def query(self, query_embedding, similarity_top_k: int, filters=None):
@@ -889,12 +1097,14 @@ class HybridRetriever(_RetrieverBase):
                 return de.retrieve_batch(queries, filters=fdn)
         # filter_dict restricts the sparse route only, filters the dense route only (retrievers.py:278,283)
         d_sparse = _per_query(fs, B, lambda v: dict(v) if v else None)
-        d_dense = _per_query(fdn, B, _filter_to_dict)
-        key_sets = {tuple(sorted(fd)) for fd in d_sparse + d_dense if fd}
+        d_dense = _per_query(fdn, B, _spec_cache())
+        key_sets = {_spec_keys(fd) for fd in d_sparse + d_dense if _spec_keys(fd)}
         if not self._fused_possible() or len(key_sets) > 1 or not self._fused_sizes():
             # (outside erh_hybrid_topk's sizes the routes run on their own: each one falls back or names its limit)
             sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs), de.retrieve_batch(queries, filters=fdn)
             return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
+        if any(isinstance(fd, _SetFilter) for fd in d_dense):
+            return self._retrieve_sets(queries, d_sparse, d_dense)
         # both routes share one engine: BM25 -> dense -> RRF([sparse, dense]) in a single device pipeline, one class column
         # per route over the shared key set (a query's two filters may still differ, or one of them be absent)
         cstate = sp._corpus_state
@@ -904,6 +1114,28 @@ class HybridRetriever(_RetrieverBase):
         ids, sc, ln = sp.engine.hybrid_topk(embs, qi, qt, k_dense=de._similarity_top_k,
                                             k_sparse=sp._similarity_top_k, K=60, topk=self.topk,
                                             filter_dir=filt_s, filter_dense=filt_d, slot=sp._slot)
+        nodes = sp._nodes
+        return [[NodeWithScore(node=nodes[i], score=float(s)) for i, s in zip(ids[b, :ln[b]], sc[b, :ln[b]])]
+                for b in range(B)]
+
+    def _retrieve_sets(self, queries: Sequence[str], d_sparse, d_dense) -> List[List[NodeWithScore]]:
+        """retrieval_type 3 with a set-valued dense filter: every step on the device, no host round trip between them -- BM25
+        top-k (class column of filter_dict) and erh_dense_topk_sets into device buffers, erh_dense_check (sub-queries answered
+        by the exhaustive path merged again), then the RRF kernel over the two device lists."""
+        sp, de = self.sparse_retriever, self.dense_retriever
+        eng, cstate = sp.engine, sp._corpus_state
+        B = len(queries)
+        filt_s = cstate.filter_column(d_sparse)
+        plan = cstate.plan(d_dense)                    # (same key set as filt_s: the caller checked; the column stays put)
+        qi, qt = queries_to_csr([sp._query_ids(q) for q in queries])
+        embs = _unit_f16(np.asarray([de._embed_model.get_query_embedding(q) for q in queries], dtype=np.float32))
+        sids, _, sln = eng.bm25_topk(qi, qt, sp._similarity_top_k, filter_dir=filt_s, device_out=True, slot=sp._slot)
+        dids, _, dln = eng.dense_topk_sets(embs, de._similarity_top_k,
+                                           [None if c == -1 else (c if isinstance(c, list) else [c]) for c in plan], device_out=True)
+        eng.dense_check()
+        fids, fsc, fln = eng.rrf_device(sids, sln, dids, dln, K=60, topk=self.topk)
+        eng.sync()
+        ids, sc, ln = fids.cpu().numpy(), fsc.cpu().numpy(), fln.cpu().numpy()
         nodes = sp._nodes
         return [[NodeWithScore(node=nodes[i], score=float(s)) for i, s in zip(ids[b, :ln[b]], sc[b, :ln[b]])]
                 for b in range(B)]

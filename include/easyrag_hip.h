@@ -30,6 +30,8 @@
  *                        metadata used by filter_dict / qdrant filters (retrievers.py:198-202,
  *                        ingestion.py:207-216, pipeline.py:301-312)
  *   erh_dense_topk       QdrantRetriever._aretrieve / _retrieve (retrievers.py:37-69)
+ *   erh_dense_topk_sets  the same with any Qdrant payload filter over the class column's keys (retrievers.py:44-47 hands
+ *                        QdrantRetriever.filters to Qdrant unchanged: MatchAny, MatchExcept, should, must_not, Range)
  *   erh_bm25_scores      BM25Retriever.get_scores (retrievers.py:128-151)
  *   erh_bm25_topk        BM25Retriever._retrieve = get_scores + filter (retrievers.py:191-220)
  *   erh_rrf              HybridRetriever.reciprocal_rank_fusion (retrievers.py:256-274)
@@ -202,6 +204,22 @@ int     erh_text_encode_mt(const erh_cutter *c, erh_vocab *v, const erh_vocab *s
 int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
                    int B, int k, const int16_t *filter_dir, int mode,
                    int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
+
+/* Dense top-k where each query may see a SET of classes: Qdrant payload filters with MatchAny / MatchExcept / should / must_not /
+ * Range, which the reference's QdrantRetriever hands to Qdrant unchanged (src/easyrag/custom/retrievers.py:44-47), evaluated on the
+ * host over the class column's distinct values (easyrag_amd/retrievers.py) into class sets.
+ *   set_ptr int32[B+1], set_cls int16[set_ptr[B]] (host CSR): query b sees the rows whose class (erh_set_doc_meta dir_id) is one of
+ *   set_cls[set_ptr[b] .. set_ptr[b+1]).  The set {-1} alone = unfiltered; an empty set = out_len[b] = 0; 32767 (or any class no
+ *   document carries) contributes nothing.  Classes within a set must be distinct and >= 0 (else ERH_ERR_INVALID, as a malformed CSR);
+ *   a set other than {-1} without a class column: ERH_ERR_STATE; k outside [1, 768]: ERH_ERR_UNSUPPORTED.
+ * Both modes.  Results: the exact top-k over the allowed rows under the mode's own ranking, canonical order, caller's numbering -- the
+ * sub-queries (query, class) run as one ordinary class-column batch of erh_dense_topk's pipeline and a merge kernel takes the top-k of
+ * their union (exact: every row has one class).  Host outputs are final on return, device outputs after erh_dense_check (which also
+ * merges again the queries whose sub-queries the exhaustive path answered).  erh_dense_diag / erh_dense_exhaustive_count then report
+ * over the call's sub-queries. */
+int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
+                        int B, int k, const int32_t *set_ptr, const int16_t *set_cls, int mode,
+                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
 
 /* BM25 top-k.  Queries as CSR of term ids (host): q_indptr int32[B+1], q_tok int32[q_indptr[B]].
  * Documents with score <= 0 are never returned (retrievers.py:195-196), so out_len[b] <= k. */
