@@ -64,6 +64,9 @@ SIGNATURES = {
     "erh_topk_row_bytes": (_i32, [_i32]),
     "erh_pack_topk": (_i32, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),
     "erh_unpack_topk": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "erh_set_shard_content": (_i32, [_vp, _i64, _vp]),
+    "erh_shard_merge_topk": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "erh_shard_rrf": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "erh_set_profiling": (_i32, [_vp, _i32]),
     "erh_get_kernel_time": (_i32, [_vp, _i32, C.POINTER(_dbl), C.POINTER(_i64)]),
     "erh_get_kernel_work": (_i32, [_vp, _i32, C.POINTER(_dbl), C.POINTER(_dbl)]),

@@ -38,7 +38,7 @@ int erh_create(int device, erh_handle **out) {
     h->device = device;
     h->n_cus = h->n_cus_dev = prop.multiProcessorCount;
     if (erh::dense_scan_init() != hipSuccess || erh::select_init() != hipSuccess || erh::bm25_init() != hipSuccess ||
-        erh::fuse_init() != hipSuccess || erh::dense_gemv_init() != hipSuccess) {   // (function attributes are per device)
+        erh::fuse_init() != hipSuccess || erh::dense_gemv_init() != hipSuccess || erh::shard_merge_init() != hipSuccess) {   // (function attributes are per device)
         delete h;
         return ERH_ERR_HIP;
     }
@@ -70,6 +70,7 @@ int erh_destroy(erh_handle *h) {
     if (h->comm || h->comm_pending) (void)erh_comm_destroy(h);
     h->gather_send.release();
     h->gather_recv.release();
+    for (DevBuf *b : {&h->shard_content, &h->sm_a_ids, &h->sm_a_len, &h->sm_b_ids, &h->sm_b_len}) b->release();
     delete h;
     return ERH_OK;
 }
@@ -1113,6 +1114,78 @@ int erh_fusion(erh_handle *h, const int32_t *ids_a, const double *scores_a, cons
     if (!h) return ERH_ERR_INVALID;
     return fuse_common(h, false, ids_a, scores_a, len_a, depth_a, ids_b, scores_b, len_b, depth_b, B, 0, topk,
                        out_ids, out_scores, out_len, io_is_device, (hipStream_t)stream);
+}
+
+// ---- corpus-sharded layout: merge / fuse what an all-gather of every slice's packed lists delivers (shard_merge.hip) ----------------
+
+int erh_set_shard_content(erh_handle *h, int64_t n_global, const int32_t *content_id) {
+    if (!h) return ERH_ERR_INVALID;
+    if (n_global < 0 || n_global > 2147483647LL || (n_global > 0 && !content_id))
+        return h->fail(ERH_ERR_INVALID, "erh_set_shard_content: bad size or null pointer");
+    for (int64_t i = 0; i < n_global; ++i)
+        if (content_id[i] < 0) return h->fail(ERH_ERR_INVALID, "erh_set_shard_content: negative content id");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (n_global > 0) {
+        HIPCHK(h, h->shard_content.ensure((size_t)n_global * 4));
+        HIPCHK(h, hipMemcpy(h->shard_content.p, content_id, (size_t)n_global * 4, hipMemcpyHostToDevice));
+    }
+    h->shard_n = n_global;
+    return ERH_OK;
+}
+
+static int shard_check(erh_handle *h, const char *who, int n_queries, int world, int k, const int32_t *id_base) {
+    if (n_queries <= 0 || world <= 0 || k <= 0 || !id_base) return h->fail(ERH_ERR_INVALID, (std::string(who) + ": null pointer or non-positive size").c_str());
+    if (!erh::shard_merge_fits(world, k))
+        return h->fail(ERH_ERR_UNSUPPORTED, (std::string(who) + ": world = " + std::to_string(world) + ", k = " + std::to_string(k) +
+                       " exceed world <= 64, k <= 1024, world * (12 k + 4) <= 163840 bytes of LDS per query").c_str());
+    for (int r = 0; r < world; ++r)
+        if (id_base[r] < 0) return h->fail(ERH_ERR_INVALID, (std::string(who) + ": negative id_base").c_str());
+    return ERH_OK;
+}
+
+int erh_shard_merge_topk(erh_handle *h, const void *rows, int n_queries, int world, int k, const int32_t *id_base,
+                         int32_t *out_ids, double *out_scores, int32_t *out_len, void *stream) {
+    if (!h) return ERH_ERR_INVALID;
+    if (!rows || !out_ids || !out_scores || !out_len) return h->fail(ERH_ERR_INVALID, "erh_shard_merge_topk: null pointer");
+    const int rc = shard_check(h, "erh_shard_merge_topk", n_queries, world, k, id_base);
+    if (rc != ERH_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    { ProfScope ps(h, st, ERH_K_FUSE, 0, 0);
+      HIPCHK(h, erh::launch_shard_merge(rows, n_queries, world, k, id_base, 2147483647, out_ids, out_scores, out_len, st)); }
+    return ERH_OK;
+}
+
+int erh_shard_rrf(erh_handle *h, const void *rows_sparse, int k_sparse, const void *rows_dense, int k_dense, int n_queries,
+                  int world, const int32_t *id_base, int K, int topk, int32_t *out_ids, double *out_scores, int32_t *out_len,
+                  void *stream) {
+    if (!h) return ERH_ERR_INVALID;
+    if (!rows_sparse || !rows_dense || !out_ids || !out_scores || !out_len || topk <= 0 || K < 0)
+        return h->fail(ERH_ERR_INVALID, "erh_shard_rrf: null pointer, topk <= 0 or K < 0");
+    if (k_dense > 768 || k_sparse > 1024 || (int64_t)k_dense + k_sparse > erh::kFuseMaxItems)
+        return h->fail(ERH_ERR_UNSUPPORTED, "erh_shard_rrf: k_dense > 768, k_sparse > 1024 or k_dense + k_sparse > 2048 (erh_hybrid_topk's limits)");
+    int rc = shard_check(h, "erh_shard_rrf", n_queries, world, k_sparse, id_base);
+    if (rc == ERH_OK) rc = shard_check(h, "erh_shard_rrf", n_queries, world, k_dense, id_base);
+    if (rc != ERH_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    // the key of the fusion: the global table when the handle holds one, else its own metadata (a handle that only merges), else the id
+    const int32_t *cid = nullptr;
+    int64_t limit = 2147483647LL;
+    if (h->shard_n > 0) { cid = h->shard_content.as<int32_t>(); limit = h->shard_n; }
+    else if (h->has_content) { cid = h->content_id.as<int32_t>(); limit = h->Nmeta; }
+    HIPCHK(h, h->sm_a_ids.ensure((size_t)n_queries * k_sparse * 4));
+    HIPCHK(h, h->sm_b_ids.ensure((size_t)n_queries * k_dense * 4));
+    HIPCHK(h, h->sm_a_len.ensure((size_t)n_queries * 4));
+    HIPCHK(h, h->sm_b_len.ensure((size_t)n_queries * 4));
+    { ProfScope ps(h, st, ERH_K_FUSE, 0, 0);
+      HIPCHK(h, erh::launch_shard_merge(rows_sparse, n_queries, world, k_sparse, id_base, (int32_t)limit, h->sm_a_ids.as<int32_t>(), nullptr,
+                                        h->sm_a_len.as<int32_t>(), st));
+      HIPCHK(h, erh::launch_shard_merge(rows_dense, n_queries, world, k_dense, id_base, (int32_t)limit, h->sm_b_ids.as<int32_t>(), nullptr,
+                                        h->sm_b_len.as<int32_t>(), st));
+      HIPCHK(h, erh::launch_rrf(h->sm_a_ids.as<int32_t>(), h->sm_a_len.as<int32_t>(), k_sparse, h->sm_b_ids.as<int32_t>(),
+                                h->sm_b_len.as<int32_t>(), k_dense, cid, n_queries, K, topk, out_ids, out_scores, out_len, st)); }
+    return ERH_OK;
 }
 
 int erh_hybrid_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,

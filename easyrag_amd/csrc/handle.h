@@ -238,6 +238,11 @@ struct erh_handle {
     std::shared_ptr<CommInitState> comm_pending;   // an init that timed out: its communicator (if it ever arrives) is destroyed later
     int opt_comm_timeout_s = 120;            // bounded wait of erh_comm_init
     DevBuf gather_send, gather_recv;
+    // corpus-sharded layout (erh_set_shard_content / erh_shard_rrf): content id of every GLOBAL document -- the handle's own metadata
+    // (erh_set_doc_meta) describes its slice -- and the merged route lists [B x k_sparse], [B x k_dense] that feed the fusion kernel
+    DevBuf shard_content;
+    int64_t shard_n = 0;
+    DevBuf sm_a_ids, sm_a_len, sm_b_ids, sm_b_len;
     // options
     int64_t opt_n0 = 32768, opt_n1 = 131072;
     int opt_n1_auto = 1;                   // snap n1 to a whole number of persistent-scan rounds (performance only)

@@ -286,4 +286,14 @@ hipError_t launch_pack_topk(const int32_t *ids, const double *sc, const int32_t 
 hipError_t launch_unpack_topk(const void *gathered, int n_queries, int world, int k, int m, int32_t *ids, double *sc,
                               int32_t *len, hipStream_t st);
 
+// ---- shard_merge.hip: corpus-sharded layout, global top k from the gathered packed rows of every rank's slice ----------------
+constexpr int kShardMaxWorld = 64;    // id_base travels as a kernel argument
+constexpr int kShardMaxK = 1024;      // erh_bm25_topk's limit on k
+hipError_t shard_merge_init();
+bool shard_merge_fits(int world, int k);   // world <= 64, k <= 1024, world * (12 k + 4) bytes of LDS <= 160 KiB
+// rows: [world][n_queries] packed rows (topk_row_bytes(k) each); id_base_host[world] is read before the call returns; ids must end up in
+// [0, id_limit) (a list ends in front of the first that does not); out_sc may be null
+hipError_t launch_shard_merge(const void *rows, int n_queries, int world, int k, const int32_t *id_base_host, int32_t id_limit,
+                              int32_t *out_ids, double *out_sc, int32_t *out_len, hipStream_t st);
+
 }  // namespace erh

@@ -475,6 +475,56 @@ class RetrievalEngine:
         self._check(self._lib.erh_unpack_topk(self._h, _ptr(gathered), int(n_queries), int(world), int(k),
                                               _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), self._stream(stream)))
 
+    # -- corpus-sharded layout (dist.py: CorpusShards): merge / fuse the gathered packed lists of every slice ----
+    def set_shard_content(self, content_id):
+        """Content id of every GLOBAL document, the key of shard_rrf (erh_set_shard_content).  The handle's own set_doc_meta
+        describes its slice; None forgets the table."""
+        cid = None if content_id is None else _np(content_id, np.int32)
+        self._check(self._lib.erh_set_shard_content(self._h, 0 if cid is None else int(cid.shape[0]), _ptr(cid)))
+
+    def _shard_rows(self, rows, n_queries: int, world: int, k: int):
+        need = int(n_queries) * int(world) * self.topk_row_bytes(k)
+        if rows.element_size() != 1 or rows.numel() != need or not rows.is_contiguous():
+            raise ValueError(f"gathered rows must be a contiguous uint8 tensor of world x n_queries x topk_row_bytes({k}) = {need} bytes")
+
+    @staticmethod
+    def _id_base(id_base, world: int) -> np.ndarray:
+        b = _np(id_base, np.int32)
+        if b.shape != (int(world),):
+            raise ValueError("id_base must have one entry per rank")
+        return b
+
+    def _outs_on(self, B, k, like, out):
+        if out is not None:
+            return out
+        import torch
+        return (torch.empty((B, k), dtype=torch.int32, device=like.device),
+                torch.empty((B, k), dtype=torch.float64, device=like.device),
+                torch.empty((B,), dtype=torch.int32, device=like.device))
+
+    def shard_merge_topk(self, rows, n_queries: int, world: int, k: int, id_base, out=None, stream=None):
+        """Gathered packed rows (device uint8 tensor: for rank r, n_queries rows of pack_topk, rank after rank) -> the global
+        [n_queries x k] lists with id_base[r] added to rank r's ids (erh_shard_merge_topk); device tensors, complete after sync()."""
+        self._shard_rows(rows, n_queries, world, k)
+        base = self._id_base(id_base, world)
+        out = self._outs_on(int(n_queries), int(k), rows, out)
+        self._check(self._lib.erh_shard_merge_topk(self._h, _ptr(rows), int(n_queries), int(world), int(k), _ptr(base),
+                                                   _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), self._stream(stream)))
+        return out
+
+    def shard_rrf(self, rows_sparse, k_sparse: int, rows_dense, k_dense: int, n_queries: int, world: int, id_base,
+                  K: int = 60, topk: int = 256, out=None, stream=None):
+        """The dual route over gathered rows: global sparse top k_sparse, global dense top k_dense, RRF([sparse, dense], K) ->
+        topk keyed by set_shard_content (erh_shard_rrf); device tensors, complete after sync()."""
+        self._shard_rows(rows_sparse, n_queries, world, k_sparse)
+        self._shard_rows(rows_dense, n_queries, world, k_dense)
+        base = self._id_base(id_base, world)
+        out = self._outs_on(int(n_queries), int(topk), rows_sparse, out)
+        self._check(self._lib.erh_shard_rrf(self._h, _ptr(rows_sparse), int(k_sparse), _ptr(rows_dense), int(k_dense),
+                                            int(n_queries), int(world), _ptr(base), int(K), int(topk), _ptr(out[0]),
+                                            _ptr(out[1]), _ptr(out[2]), self._stream(stream)))
+        return out
+
     # -- measurement ------------------------------------------------------------------------------
     def sync(self, stream=None):
         self._check(self._lib.erh_sync(self._h, self._stream(stream)))

@@ -172,6 +172,31 @@ def build_bm25_index_from_ids(corpus_ids: Optional[Sequence[Sequence[int]]] = No
     return _finish(variant, n_docs, n_vocab, indptr, doc, tf, doc_lens, order, k1, b, epsilon, compute_payload)
 
 
+def slice_bm25_index(index: BM25Index, lo: int, hi: int) -> BM25Index:
+    """The postings of documents [lo, hi) as an index of their own, documents renumbered from 0, for one slice of a
+    corpus-sharded layout (dist.py: CorpusShards).  `idf`, `avgdl`, `average_idf`, `k1`, `b`, `epsilon`, `n_vocab` and `vocab`
+    stay the PARENT's: a payload is a function of (idf[t], tf, dl, avgdl, k1, b) only, so the slice scores its documents
+    exactly as the parent does, and query term ids mean the same on every slice.  The payload is sliced when the parent holds
+    one.  Vectorised: one mask over the postings and its running count."""
+    lo, hi = int(lo), int(hi)
+    if not 0 <= lo < hi <= index.n_docs:
+        raise ValueError(f"slice [{lo}, {hi}) must be a non-empty range of the index's {index.n_docs} documents")
+    if index.n_postings is not None and index.doc_ids.shape[0] != index.nnz:
+        raise ValueError("the index's postings live on the device only; fetch them first (build_bm25(fetch=True))")
+    doc = index.doc_ids
+    mask = (doc >= lo) & (doc < hi)
+    kept = np.zeros(doc.shape[0] + 1, np.int64)               # kept[p] = postings of the slice in front of posting p
+    np.cumsum(mask, out=kept[1:])
+    indptr = np.ascontiguousarray(kept[np.asarray(index.indptr, dtype=np.int64)])
+    has_payload = index.payload.shape[0] == doc.shape[0] and doc.shape[0] > 0
+    return BM25Index(variant=index.variant, n_docs=hi - lo, n_vocab=index.n_vocab, indptr=indptr,
+                     doc_ids=(doc[mask] - lo).astype(np.int32), tf=np.ascontiguousarray(index.tf[mask]),
+                     doc_len=np.ascontiguousarray(index.doc_len[lo:hi]), idf=index.idf, avgdl=index.avgdl, k1=index.k1,
+                     b=index.b, epsilon=index.epsilon,
+                     payload=np.ascontiguousarray(index.payload[mask]) if has_payload else index.payload[:0],
+                     vocab=index.vocab, average_idf=index.average_idf)
+
+
 def vocab_ids_python(corpus: Sequence[Sequence[Hashable]]):
     """Tokenised corpus -> (vocab {token: id by first appearance}, flat int32 id stream, int32 tokens per document) with a
     Python dict: the general path (any hashable token) and the checker of the native one."""

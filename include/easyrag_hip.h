@@ -280,6 +280,35 @@ int erh_pack_topk(erh_handle *h, const int32_t *ids, const double *scores, const
 int erh_unpack_topk(erh_handle *h, const void *gathered_rows, int n_queries, int world, int k,
                     int32_t *out_ids, double *out_scores, int32_t *out_len, void *stream);
 
+/* ---- corpus-sharded layout: every GPU holds a contiguous slice of the corpus ------------------
+ * The other multi-GPU layout; the reference has no counterpart (single process, one corpus:
+ * src/main.py:48-52).  Rank r holds the rows [id_base[r], id_base[r + 1]) of the corpus in a handle of its own, answers
+ * ALL n_queries queries on it (erh_dense_topk / erh_bm25_topk with device outputs, then erh_dense_check), packs each
+ * route's lists with erh_pack_topk(b_local = rows = n_queries) and all-gathers the rows.  A score depends on (query,
+ * document) only and every list is canonical (score descending, id ascending), so the canonical top k of the union of
+ * the gathered lists IS the unsharded call's list, bit for bit (easyrag_amd/csrc/shard_merge.hip).
+ *
+ * erh_shard_merge_topk: DEVICE buffers, enqueue-only on `stream`.  rows = what the gather delivers: for rank r,
+ *   n_queries packed rows of erh_topk_row_bytes(k) bytes, rank after rank.  Output row q = the canonical top k of the
+ *   union over r of rank r's list for query q with id_base[r] added to its ids; equal scores order by global id.  Lists
+ *   may be shorter than k or empty; padding is id -1 / score 0.  id_base is a HOST array of `world` entries >= 0, read
+ *   before the call returns.  Limits: k <= 1024, world <= 64 and world * (12 k + 4) <= 163840 bytes (the lists of one
+ *   query are merged in the LDS of one CU: 8 x 1024 and 13 x 1024 fit, 14 x 1024 does not): ERH_ERR_UNSUPPORTED beyond.
+ * erh_shard_rrf: the dual route.  Merges the sparse rows to the global top k_sparse and the dense rows to the global top
+ *   k_dense (same kernel, into buffers of the handle) and fuses them with erh_rrf's kernel and rules:
+ *   RRF([sparse, dense], K) -> topk, keyed by the content of the GLOBAL document.  Accepts every (k_dense, k_sparse)
+ *   erh_hybrid_topk accepts.  No host round trip, no allocation after the first call of a shape.
+ * erh_set_shard_content: content id of every global document (host array) for erh_shard_rrf.  A slice handle's own
+ *   erh_set_doc_meta describes ITS rows (the dir column of its slice), so the global table is kept apart; a handle
+ *   without one fuses by its erh_set_doc_meta content ids (a handle that only merges), or by document id if it has none.
+ *   A gathered id outside the table ends its list there (never a read out of bounds).  n_global = 0 forgets the table. */
+int erh_set_shard_content(erh_handle *h, int64_t n_global, const int32_t *content_id);
+int erh_shard_merge_topk(erh_handle *h, const void *rows, int n_queries, int world, int k, const int32_t *id_base,
+                         int32_t *out_ids, double *out_scores, int32_t *out_len, void *stream);
+int erh_shard_rrf(erh_handle *h, const void *rows_sparse, int k_sparse, const void *rows_dense, int k_dense, int n_queries,
+                  int world, const int32_t *id_base, int K, int topk, int32_t *out_ids, double *out_scores, int32_t *out_len,
+                  void *stream);
+
 /* ---- measurement / diagnostics --------------------------------------------------------- */
 
 /* Kernel timing with HIP events on the launch stream.  Kernel classes: */
