@@ -38,7 +38,8 @@ int erh_create(int device, erh_handle **out) {
     h->device = device;
     h->n_cus = h->n_cus_dev = prop.multiProcessorCount;
     if (erh::dense_scan_init() != hipSuccess || erh::select_init() != hipSuccess || erh::bm25_init() != hipSuccess ||
-        erh::fuse_init() != hipSuccess || erh::dense_gemv_init() != hipSuccess || erh::shard_merge_init() != hipSuccess) {   // (function attributes are per device)
+        erh::fuse_init() != hipSuccess || erh::dense_gemv_init() != hipSuccess || erh::shard_merge_init() != hipSuccess ||
+        erh::dense_rows_init() != hipSuccess) {   // (function attributes are per device)
         delete h;
         return ERH_ERR_HIP;
     }
@@ -63,7 +64,8 @@ int erh_destroy(erh_handle *h) {
                       &h->hy_sids, &h->hy_ssc, &h->hy_slen, &h->hy_dids, &h->hy_dsc, &h->hy_dlen,
                       &h->fa_ids, &h->fa_sc, &h->fa_len, &h->fb_ids, &h->fb_sc, &h->fb_len,
                       &h->scores_tmp, &h->scores_wide, &h->dbg, &h->dstats, &h->dir_pos, &h->seed_need, &h->bad, &h->ex_ws, &h->bm_redo, &h->fin_ws, &h->dir_rng, &h->Xb, &h->blk_tmp, &h->blk_ids, &h->r_q, &h->r_ids, &h->r_sc, &h->r_len, &h->r_flags, &h->r_tab, &h->r_q16, &h->bm_fin_ids, &h->bm_fin_cnt,
-                      &h->s_tab, &h->s_q, &h->s_ids, &h->s_sc, &h->s_len};
+                      &h->s_tab, &h->s_q, &h->s_ids, &h->s_sc, &h->s_len, &h->lpart_sc, &h->lpart_ids, &h->lpart_len, &h->l_redo,
+                      &h->rw_tab, &h->rw_q, &h->rw_q16, &h->rw_qn, &h->rw_s64, &h->rw_ids, &h->rw_sc, &h->rw_len};
     for (DevBuf *b : bufs) b->release();
     if (h->r_flags_host) (void)hipHostFree(h->r_flags_host);
     for (auto &b : h->bm) b.release();
@@ -105,6 +107,7 @@ int erh_set_option(erh_handle *h, const char *name, int64_t value) {
     if (!strcmp(name, "bm25_split_finish")) { h->opt_bm25_split_finish = value != 0; return ERH_OK; }
     if (!strcmp(name, "bm25_mixed")) { h->opt_bm25_mixed = value != 0; return ERH_OK; }
     if (!strcmp(name, "bm25_long_segs")) { if (value < 1 || value > 16) return h->fail(ERH_ERR_INVALID, "bm25_long_segs"); h->opt_bm25_long_segs = (int)value; return ERH_OK; }
+    if (!strcmp(name, "dense_rows_ws_mb")) { if (value < 0 || value > 65536) return h->fail(ERH_ERR_INVALID, "dense_rows_ws_mb"); h->opt_rows_ws_mb = value; return ERH_OK; }
     if (!strcmp(name, "dense_route_ridge")) { if (value < 1 || value > 4096) return h->fail(ERH_ERR_INVALID, "dense_route_ridge"); h->opt_route_ridge = value; return ERH_OK; }
     if (!strcmp(name, "dense_group_sample")) { h->opt_dense_group_sample = value != 0; return ERH_OK; }
     if (!strcmp(name, "dense_group_launch")) { h->opt_dense_group_launch = value != 0; return ERH_OK; }
@@ -228,7 +231,8 @@ int erh_get_stat(erh_handle *h, const char *name, int64_t *value) {
         {"dense_scan_gemv_launches", T.dense_scan_gemv}, {"dense_scan_tile_launches", T.dense_scan_tile},
         {"dense_sample_passes", T.dense_sample_passes}, {"dense_tile384_nomem", T.dense_tile384_nomem},
         {"bm25_calls", T.bm25_calls}, {"hybrid_calls", T.hybrid_calls}, {"dense_block_groups", T.dense_block_groups},
-        {"dense_grouped_launches", T.dense_grouped_launches}, {"bm25_mixed_launches", T.bm25_mixed_launches}};
+        {"dense_grouped_launches", T.dense_grouped_launches}, {"bm25_mixed_launches", T.bm25_mixed_launches},
+        {"dense_rows_calls", T.dense_rows_calls}, {"dense_rows_short_launches", T.dense_rows_short}, {"dense_rows_long_launches", T.dense_rows_long}};
     for (const auto &e : host)
         if (!strcmp(name, e.n)) { *value = e.v; return ERH_OK; }
     if (!strcmp(name, "dense_candidates_last_call")) {
@@ -999,6 +1003,147 @@ int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_devi
         if (rc != ERH_OK) return rc;
         return copy_out(h, B, k, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
     }
+    return ERH_OK;
+}
+
+// Explicit row lists (dense_rows.hip).  The call keeps to buffers of its own (rw_*) and touches neither the flag words nor the record of the
+// last scan-route call: it has no threshold to verify, so nothing of it is left for erh_dense_check, and a device-output dense call that is
+// still waiting for its check finds everything as it left it.  Queries are prepared by the same kernel as on every other route (the fp16
+// values the scores are defined on).  Lists of at most kDenseRowsShortMax rows: one launch for all their queries; longer ones: score + select
+// launches per chunk of queries whose score spans fit the work space -- chunks follow each other on the stream, which is what orders the reuse
+// of the span buffer; the work-item tables of the whole call go up once.
+int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q, int B, int k,
+                        int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
+                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
+    if (!h) return ERH_ERR_INVALID;
+    if (!h->X.p || h->N <= 0) return h->fail(ERH_ERR_STATE, "erh_dense_topk_rows before erh_set_dense");
+    if (!q || !out_ids || !out_scores || !out_len || !list_of || B <= 0 || n_lists < 0 || (n_lists > 0 && !list_ptr))
+        return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: null pointer, non-positive B or negative n_lists");
+    if (q_dtype != ERH_F16 && q_dtype != ERH_F32) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: q_dtype");
+    if (k < 1 || k > 768) return h->fail(ERH_ERR_UNSUPPORTED, "erh_dense_topk_rows: k outside [1, 768]");
+    const int64_t N = h->N;
+    const int d = h->d;
+    // the lists: a monotone CSR from 0, every list strictly ascending inside [0, N)
+    int64_t total = 0;
+    if (n_lists > 0) {
+        if (list_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: list_ptr[0] != 0");
+        for (int l = 0; l < n_lists; ++l)
+            if (list_ptr[l + 1] < list_ptr[l]) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: list_ptr decreases");
+        total = list_ptr[n_lists];
+        if (total > 0 && !list_rows) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: null list_rows");
+        for (int l = 0; l < n_lists; ++l)
+            for (int64_t i = list_ptr[l]; i < list_ptr[l + 1]; ++i) {
+                const int32_t r = list_rows[i];
+                if (r < 0 || (int64_t)r >= N) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: row outside [0, N)");
+                if (i > list_ptr[l] && r <= list_rows[i - 1]) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: rows of a list must be strictly ascending");
+            }
+    }
+    for (int b = 0; b < B; ++b)
+        if (list_of[b] < -1 || list_of[b] >= n_lists) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: list_of outside [-1, n_lists)");
+    auto len_of = [&](int b) -> int64_t { const int l = list_of[b]; return l < 0 ? 0 : list_ptr[l + 1] - list_ptr[l]; };
+    // shapes: the short one for every query whose list fits the LDS sort, the long one for the others, grouped by list
+    std::vector<int32_t> q_short, q_long;
+    for (int b = 0; b < B; ++b) (len_of(b) <= erh::kDenseRowsShortMax ? q_short : q_long).push_back(b);
+    std::stable_sort(q_long.begin(), q_long.end(), [&](int32_t a, int32_t b) { return list_of[a] < list_of[b]; });
+    if (!q_long.empty() && erh::dense_rows_score_lds(d) > 128 * 1024)
+        return h->fail(ERH_ERR_UNSUPPORTED, "erh_dense_topk_rows: d too large for lists longer than 2048 rows");
+    // chunks of long queries (whole list groups of <= kDenseRowsGroup where they fit) whose spans fit the work space; span offsets are relative
+    // to the chunk
+    const int64_t ws_doubles = std::max<int64_t>((h->opt_rows_ws_mb << 20) / 8, N);
+    struct Chunk { int q0, q1; int64_t item0, item1, doubles; };
+    std::vector<Chunk> chunks;
+    std::vector<int64_t> span_off((size_t)B, 0);
+    std::vector<erh::ErhRowsItem> items;
+    {
+        size_t i = 0;
+        Chunk c{0, 0, 0, 0, 0};
+        while (i < q_long.size()) {
+            const int l = list_of[q_long[i]];
+            const int64_t len = list_ptr[l + 1] - list_ptr[l];
+            size_t j = i;
+            while (j < q_long.size() && j - i < (size_t)erh::kDenseRowsGroup && list_of[q_long[j]] == l) ++j;
+            int ng = (int)(j - i);
+            if (c.doubles + len > ws_doubles && c.q1 > c.q0) {            // the chunk is full: it ends in front of this group
+                c.item1 = (int64_t)items.size();
+                chunks.push_back(c);
+                c = Chunk{(int)i, (int)i, (int64_t)items.size(), 0, 0};
+            }
+            ng = (int)std::min<int64_t>(ng, std::max<int64_t>(1, (ws_doubles - c.doubles) / len));   // (len <= N <= ws_doubles: at least one)
+            for (int g = 0; g < ng; ++g) { span_off[(size_t)q_long[i + g]] = c.doubles; c.doubles += len; }
+            for (int64_t i0 = 0; i0 < len; i0 += erh::kDenseRowsSeg)
+                items.push_back(erh::ErhRowsItem{list_ptr[l] + i0, (int32_t)std::min<int64_t>(erh::kDenseRowsSeg, len - i0), (int32_t)i0, (int32_t)i, ng});
+            i += (size_t)ng;
+            c.q1 = (int)i;
+        }
+        if (c.q1 > c.q0) { c.item1 = (int64_t)items.size(); chunks.push_back(c); }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    // work space first: a call that cannot have it enqueues nothing
+    int64_t need = 0;
+    for (const Chunk &c : chunks) need = std::max(need, c.doubles);
+    const size_t o_ptr = 0, o_span = o_ptr + ((size_t)n_lists + 1) * 8, o_items = o_span + (size_t)B * 8,
+                 o_rows = o_items + items.size() * sizeof(erh::ErhRowsItem), o_of = o_rows + (size_t)total * 4, o_short = o_of + (size_t)B * 4,
+                 o_long = o_short + q_short.size() * 4, tab_bytes = o_long + q_long.size() * 4;
+    const size_t q_bytes = (size_t)B * d * (q_dtype == ERH_F16 ? 2 : 4);
+    {
+        hipError_t e = hipSuccess;
+        if (need > 0) e = h->rw_s64.ensure((size_t)need * 8);
+        if (e == hipSuccess) e = h->rw_tab.ensure(tab_bytes);
+        if (e == hipSuccess) e = h->rw_q16.ensure((size_t)B * d * 2);
+        if (e == hipSuccess) e = h->rw_qn.ensure((size_t)B * 4);
+        if (e == hipSuccess && !q_is_device) e = h->rw_q.ensure(q_bytes);
+        if (e == hipSuccess && !out_is_device) {
+            e = h->rw_ids.ensure((size_t)B * k * 4);
+            if (e == hipSuccess) e = h->rw_sc.ensure((size_t)B * k * 8);
+            if (e == hipSuccess) e = h->rw_len.ensure((size_t)B * 4);
+        }
+        if (e != hipSuccess) { (void)hipGetLastError(); return h->fail(ERH_ERR_NOMEM, "erh_dense_topk_rows: work space", e); }
+    }
+    {
+        std::vector<char> tab(tab_bytes);
+        const int64_t zero = 0;
+        memcpy(tab.data() + o_ptr, n_lists > 0 ? (const void *)list_ptr : (const void *)&zero, ((size_t)n_lists + 1) * 8);
+        memcpy(tab.data() + o_span, span_off.data(), (size_t)B * 8);
+        if (!items.empty()) memcpy(tab.data() + o_items, items.data(), items.size() * sizeof(erh::ErhRowsItem));
+        if (total > 0) memcpy(tab.data() + o_rows, list_rows, (size_t)total * 4);
+        memcpy(tab.data() + o_of, list_of, (size_t)B * 4);
+        if (!q_short.empty()) memcpy(tab.data() + o_short, q_short.data(), q_short.size() * 4);
+        if (!q_long.empty()) memcpy(tab.data() + o_long, q_long.data(), q_long.size() * 4);
+        HIPCHK(h, hipMemcpyAsync(h->rw_tab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
+        if (!q_is_device) HIPCHK(h, hipMemcpyAsync(h->rw_q.p, q, q_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipStreamSynchronize(st));               // (`tab` is pageable memory of this scope)
+    }
+    const char *T = h->rw_tab.as<char>();
+    const int64_t *d_ptr = reinterpret_cast<const int64_t *>(T + o_ptr), *d_span = reinterpret_cast<const int64_t *>(T + o_span);
+    const erh::ErhRowsItem *d_items = reinterpret_cast<const erh::ErhRowsItem *>(T + o_items);
+    const int32_t *d_rows = reinterpret_cast<const int32_t *>(T + o_rows), *d_of = reinterpret_cast<const int32_t *>(T + o_of),
+                  *d_short = reinterpret_cast<const int32_t *>(T + o_short), *d_long = reinterpret_cast<const int32_t *>(T + o_long);
+    int32_t *d_ids = out_ids; double *d_sc = out_scores; int32_t *d_len = out_len;
+    if (!out_is_device) { d_ids = h->rw_ids.as<int32_t>(); d_sc = h->rw_sc.as<double>(); d_len = h->rw_len.as<int32_t>(); }
+    const _Float16 *X = h->X.as<_Float16>();
+    const _Float16 *Q16 = h->rw_q16.as<_Float16>();
+    h->stats.dense_rows_calls += 1;
+    { ProfScope ps(h, st, ERH_K_DENSE_SELECT, 0, 0);
+      HIPCHK(h, erh::launch_prep_queries(q_is_device ? q : h->rw_q.p, q_dtype, normalize_q, B, B, d, h->rw_q16.as<_Float16>(), h->rw_qn.as<float>(),
+                                         nullptr, nullptr, st)); }
+    if (!q_short.empty()) {
+        int64_t n_rows = 0;
+        for (int32_t b : q_short) n_rows += len_of(b);
+        ProfScope ps(h, st, ERH_K_DENSE_SCAN, (double)n_rows * d * 2, 2.0 * (double)n_rows * d);
+        HIPCHK(h, erh::launch_dense_rows_short(X, N, d, h->pos_mul, Q16, d_rows, d_ptr, d_of, d_short, (int)q_short.size(), k, d_ids, d_sc, d_len, st));
+        h->stats.dense_rows_short += 1;
+    }
+    for (const Chunk &c : chunks) {
+        { ProfScope ps(h, st, ERH_K_DENSE_SCAN, 0, (double)c.doubles * d * 2.0);
+          HIPCHK(h, erh::launch_dense_rows_score(X, N, d, h->pos_mul, Q16, d_rows, d_items + c.item0, (int)(c.item1 - c.item0), d_long, d_span,
+                                                 h->rw_s64.as<double>(), st)); }
+        { ProfScope ps(h, st, ERH_K_DENSE_SELECT, (double)c.doubles * 8, 0);
+          HIPCHK(h, erh::launch_dense_rows_select(h->rw_s64.as<double>(), d_span, d_rows, d_ptr, d_of, d_long + c.q0, c.q1 - c.q0, k, d_ids, d_sc,
+                                                  d_len, st)); }
+        h->stats.dense_rows_long += 1;
+    }
+    if (!out_is_device) return copy_out(h, B, k, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
     return ERH_OK;
 }
 

@@ -194,6 +194,11 @@ struct erh_handle {
         double acc_maxerr = 0; int32_t acc_uncert = 0, acc_exhaustive = 0;   // diag of the chunks checked before the last one
     } sets;
     DevBuf s_tab, s_q, s_ids, s_sc, s_len;   // s_tab: sub_ptr int32[B+1] | source row int32[n_sub] | class int16[n_sub], one upload
+    // erh_dense_topk_rows (dense_rows.hip): buffers of its own, so that a rows call between a device-output dense call and its erh_dense_check
+    // leaves that call's query block, flag words and lists alone.  rw_tab: ONE upload per call -- list_ptr | span offsets | work items | rows |
+    // list_of | short-shape queries | long-shape queries; rw_s64: the long shape's score spans (opt_rows_ws_mb, at least one list of N rows)
+    DevBuf rw_tab, rw_q, rw_q16, rw_qn, rw_s64, rw_ids, rw_sc, rw_len;
+    int64_t opt_rows_ws_mb = 256;
     bool dense_corrected = false;            // dense_check_flags changed result rows (exhaustive rounds or a group run again)
     DevBuf dir_rng;                          // {first document, last + 1} of every dir class (erh_set_doc_meta): a filtered BM25 query walks those tiles only
     int dir_rng_n = 0;
@@ -230,7 +235,7 @@ struct erh_handle {
     struct Stats {
         int64_t dense_calls = 0, dense_scan_pp5 = 0, dense_scan_pp3 = 0, dense_scan_gemv = 0, dense_scan_tile = 0,
                 dense_sample_passes = 0, dense_tile384_nomem = 0, bm25_calls = 0, hybrid_calls = 0, dense_block_groups = 0,
-                dense_grouped_launches = 0, bm25_mixed_launches = 0;
+                dense_grouped_launches = 0, bm25_mixed_launches = 0, dense_rows_calls = 0, dense_rows_short = 0, dense_rows_long = 0;
     } stats;
     // multi-GPU exchange (erh_comm_* / erh_allgather_topk): RCCL communicator + packed send / receive rows
     void *comm = nullptr;

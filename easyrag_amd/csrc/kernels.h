@@ -296,4 +296,28 @@ bool shard_merge_fits(int world, int k);   // world <= 64, k <= 1024, world * (1
 hipError_t launch_shard_merge(const void *rows, int n_queries, int world, int k, const int32_t *id_base_host, int32_t id_limit,
                               int32_t *out_ids, double *out_sc, int32_t *out_len, hipStream_t st);
 
+// ---- dense_rows.hip: exact top k over explicit per-query row lists (erh_dense_topk_rows) -------------------------------------------------
+constexpr int kDenseRowsShortMax = 2048;   // lists up to this length: one launch, one workgroup per query (scores sorted in LDS)
+constexpr int kDenseRowsGroup = 8;         // long shape: queries sharing a list that share its row loads in one workgroup
+constexpr int kDenseRowsSeg = 1024;        // ... rows of a list per work item
+// One work item of the long shape's score kernel: rows[row_off .. row_off + n_rows) are the rows i0 .. of a list, scored for the queries
+// qord[q_at .. q_at + nq) (nq <= kDenseRowsGroup, all on that list) into S64[span_off[query] + i0 + r].
+struct ErhRowsItem {
+    int64_t row_off;
+    int32_t n_rows, i0, q_at, nq;
+};
+static_assert(sizeof(ErhRowsItem) == 24, "ErhRowsItem layout");
+hipError_t dense_rows_init();
+size_t dense_rows_score_lds(int d);        // dynamic LDS of the score kernel: must stay within 128 KiB
+// rows / list_ptr / list_of: the call's lists on the device (list_of[b] = -1: no rows); qsel[0 .. n_q): the queries this launch answers
+hipError_t launch_dense_rows_short(const _Float16 *X, int64_t N, int d, int64_t pos_mul, const _Float16 *Q16, const int32_t *rows,
+                                   const int64_t *list_ptr, const int32_t *list_of, const int32_t *qsel, int n_q, int k, int32_t *out_ids,
+                                   double *out_sc, int32_t *out_len, hipStream_t st);
+hipError_t launch_dense_rows_score(const _Float16 *X, int64_t N, int d, int64_t pos_mul, const _Float16 *Q16, const int32_t *rows,
+                                   const ErhRowsItem *items, int n_items, const int32_t *qord, const int64_t *span_off, double *S64,
+                                   hipStream_t st);
+hipError_t launch_dense_rows_select(const double *S64, const int64_t *span_off, const int32_t *rows, const int64_t *list_ptr,
+                                    const int32_t *list_of, const int32_t *qord, int n_q, int k, int32_t *out_ids, double *out_sc,
+                                    int32_t *out_len, hipStream_t st);
+
 }  // namespace erh

@@ -339,6 +339,47 @@ class RetrievalEngine:
                                                   1 if device_out else 0, self._stream(stream)))
         return ids, sc, ln
 
+    @staticmethod
+    def lists_to_csr(lists, list_of, B: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Row lists (int arrays, each strictly ascending) + the list of every query -> (list_ptr int64[n+1], list_rows int32[...],
+        list_of int32[B]).  list_of None: query b uses list b; an entry of -1: no rows."""
+        arrs = [np.ascontiguousarray(np.asarray(l).reshape(-1), dtype=np.int64) for l in lists]
+        if list_of is None:
+            if len(arrs) != B:
+                raise ValueError("lists must have one entry per query when list_of is not given")
+            lo = np.arange(B, dtype=np.int32)
+        else:
+            lo = np.ascontiguousarray(np.asarray(list_of).reshape(-1), dtype=np.int32)
+            if lo.shape[0] != B:
+                raise ValueError("list_of must have one entry per query")
+        ptr = np.zeros(len(arrs) + 1, np.int64)
+        if arrs:
+            np.cumsum([a.size for a in arrs], out=ptr[1:])
+        rows = np.concatenate(arrs) if arrs else np.zeros(0, np.int64)
+        if rows.size and (rows.min() < -2**31 or rows.max() >= 2**31):
+            raise ValueError("row ids must fit int32")
+        return ptr, np.ascontiguousarray(rows, dtype=np.int32), lo
+
+    def dense_topk_rows(self, q, k: int, lists, list_of=None, normalize_q: bool = False, device_out: bool = False, stream=None):
+        """Exact dense top-k of query b over the rows lists[list_of[b]] and nothing else (erh_dense_topk_rows): every listed row gets its
+        pinned fp64 score, ranked by (score desc, row id asc).  Each list must be strictly ascending inside [0, N).  list_of None: query b
+        uses list b; -1: no rows.  device_out: results are final after sync() -- no dense_check() is needed."""
+        q, dt, is_dev, B = self._q_desc(q)
+        return self.dense_topk_rows_csr(q, k, *self.lists_to_csr(lists, list_of, B), normalize_q=normalize_q, device_out=device_out,
+                                        stream=stream)
+
+    def dense_topk_rows_csr(self, q, k: int, ptr, rows, lo, normalize_q: bool = False, device_out: bool = False, stream=None):
+        """dense_topk_rows on the C entry's own tables (lists_to_csr's result): a caller that sends the same lists again builds them once."""
+        q, dt, is_dev, B = self._q_desc(q)
+        ptr, rows, lo = _np(ptr, np.int64), _np(rows, np.int32), _np(lo, np.int32)
+        if lo.shape[0] != B:
+            raise ValueError("list_of must have one entry per query")
+        ids, sc, ln = self._outs(B, k, device_out)
+        self._check(self._lib.erh_dense_topk_rows(self._h, _ptr(q), dt, is_dev, 1 if normalize_q else 0, B, int(k),
+                                                  int(ptr.shape[0] - 1), _ptr(ptr), _ptr(rows), _ptr(lo), _ptr(ids), _ptr(sc), _ptr(ln),
+                                                  1 if device_out else 0, self._stream(stream)))
+        return ids, sc, ln
+
     def bm25_topk(self, q_indptr, q_tok, k: int, filter_dir=None, device_out: bool = False, stream=None,
                   slot: Optional[int] = None):
         self._select(slot)
@@ -562,7 +603,8 @@ class RetrievalEngine:
 
     STAT_NAMES = ("dense_calls", "bm25_calls", "hybrid_calls", "dense_scan_pp5_launches", "dense_scan_pp3_launches",
                   "dense_scan_gemv_launches", "dense_scan_tile_launches", "dense_sample_passes", "dense_tile384_nomem",
-                  "dense_exhaustive_queries", "bm25_redo_segments", "dense_block_groups", "dense_grouped_launches", "bm25_mixed_launches")
+                  "dense_exhaustive_queries", "bm25_redo_segments", "dense_block_groups", "dense_grouped_launches", "bm25_mixed_launches",
+                  "dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches")
 
     def stat(self, name: str) -> int:
         """One counter of erh_get_stat (which kernels answered the calls since the last reset_stats)."""

@@ -144,6 +144,11 @@ def _as_bundle(q) -> QueryBundle:
     return q if isinstance(q, QueryBundle) else QueryBundle(query_str=str(q))
 
 
+class _TooManyClasses(ValueError):
+    """More distinct value tuples than the int16 class column can number.  The sparse route reports it; the dense route serves such a
+    filter through explicit row lists instead (HipVectorStore.query_batch)."""
+
+
 class _MetaClasses:
     """Per-document class ids for an equality filter over a fixed set of metadata keys."""
 
@@ -157,7 +162,7 @@ class _MetaClasses:
             if j is None:
                 j = len(self.values)
                 if j >= 32000:
-                    raise ValueError("too many distinct filter values")
+                    raise _TooManyClasses("too many distinct filter values")
                 self.values[v] = j
             ids[i] = j
         self.ids = ids
@@ -371,6 +376,54 @@ class _FilteredCorpus:
             self._classes = cache[keys]
             self._push_meta()
         return self._classes
+
+    def too_many_values(self, keys: tuple) -> bool:
+        """True when the nodes carry more distinct value tuples over `keys` than a class column can number (the walk that finds out
+        runs once per key set; the table it builds otherwise is the one the class-column path uses)."""
+        known = self.__dict__.setdefault("_too_many", {})
+        if keys not in known:
+            cache = self.__dict__.setdefault("_class_tables", {})
+            try:
+                if keys not in cache:
+                    cache[keys] = _MetaClasses(self.nodes, keys)
+                known[keys] = False
+            except _TooManyClasses:
+                known[keys] = True
+        return known[keys]
+
+    def rows_matching(self, spec) -> np.ndarray:
+        """Ascending row ids whose metadata satisfies `spec` (a dict of the equality shape or a _SetFilter), by evaluating the filter on
+        every node: an O(N) host walk per DISTINCT filter, cached like class_set's evaluations.  For key sets without a class table."""
+        key = ("eq", tuple(sorted(spec.items(), key=repr))) if isinstance(spec, dict) else spec.node
+        cache = self.__dict__.setdefault("_rows_cache", {})
+        hit = cache.get(key)
+        if hit is None:
+            if isinstance(spec, dict):                     # the class column's equality: an absent key equals None
+                items = list(spec.items())
+                keep = [i for i, n in enumerate(self.nodes) if all(n.metadata.get(k) == v for k, v in items)]
+            else:
+                keys = spec.keys
+                keep = [i for i, n in enumerate(self.nodes)
+                        if _holds(spec.node, {k: n.metadata[k] for k in keys if n.metadata.get(k) is not None})]
+            hit = np.asarray(keep, np.int64)
+            if len(cache) >= 256:
+                cache.clear()
+            cache[key] = hit
+        return hit
+
+    def class_rows(self, table: "_MetaClasses", c: int) -> np.ndarray:
+        """Ascending rows of class c of `table`, cached per class table."""
+        cache = table.__dict__.setdefault("_rows_of_class", {})
+        hit = cache.get(c)
+        if hit is None:
+            hit = cache[c] = np.flatnonzero(table.ids == c).astype(np.int64)
+        return hit
+
+    def class_counts(self, table: "_MetaClasses") -> np.ndarray:
+        cnt = table.__dict__.get("_counts")
+        if cnt is None:
+            cnt = table.__dict__["_counts"] = np.bincount(table.ids.astype(np.int64), minlength=len(table.values))
+        return cnt
 
     def class_set(self, spec: "_SetFilter") -> Optional[List[int]]:
         """Classes (of the column over spec.keys) whose value tuple satisfies the filter, ascending; None = every class.  The
@@ -677,14 +730,119 @@ class HipVectorStore:
             raise ValueError(f"{npy}: shape / dtype differ from its meta file")
         return cls(nodes, x, engine=engine, normalize=False)
 
-    def query_batch(self, query_embeddings, similarity_top_k: int, filters=None, mode: int = _lib.ERH_DENSE_EXACT):
-        """`filters`: one filter for the whole batch (None, dict, qdrant Filter) or a list with one filter per query."""
+    rows_route_max = 0     # > 0: a filtered query whose filter allows at most this many rows goes through the rows entry (opt-in; results identical)
+
+    def query_batch(self, query_embeddings, similarity_top_k: int, filters=None, mode: int = _lib.ERH_DENSE_EXACT, rows=None):
+        """`filters`: one filter for the whole batch (None, dict, qdrant Filter) or a list with one filter per query.
+        `rows`: restrict queries to explicit row ids (positions in the node list) -- one id array for every query, or a list parallel to
+        the queries whose entries are an id array or None.  Such a query ranks exactly those rows (erh_dense_topk_rows; with a filter as
+        well: the rows that also pass it), the others run as without the argument, and the two parts are scattered into one result."""
         q = _unit_f16(query_embeddings)
         B, k = q.shape[0], int(similarity_top_k)
         if not 1 <= k <= DENSE_MAX_K:
             # no exact host fall-back: the chunk matrix lives on the device only
             raise ValueError(f"dense similarity_top_k must lie in [1, {DENSE_MAX_K}], got {k}")
+        if rows is not None and mode != _lib.ERH_DENSE_EXACT:
+            raise ValueError("rows= ranks by the pinned fp64 score of every listed row: ERH_DENSE_EXACT only")
         dicts = _per_query(filters, B, _spec_cache())
+        rows_q, dicts = self._resolve_rows(dicts, rows, B, mode)
+        with_rows = [b for b in range(B) if rows_q[b] is not None]
+        if not with_rows:
+            return self._query_filtered(q, k, dicts, mode)
+        lists, list_of = self._rows_lists([rows_q[b] for b in with_rows])
+        if len(with_rows) == B:
+            return self.engine.dense_topk_rows(q, k, lists, list_of=list_of)
+        ids, sc, ln = np.full((B, k), -1, np.int32), np.zeros((B, k), np.float64), np.zeros(B, np.int32)
+        rest = [b for b in range(B) if rows_q[b] is None]
+        ids[rest], sc[rest], ln[rest] = self._query_filtered(q[rest], k, [dicts[b] for b in rest], mode)
+        ids[with_rows], sc[with_rows], ln[with_rows] = self.engine.dense_topk_rows(q[with_rows], k, lists, list_of=list_of)
+        return ids, sc, ln
+
+    def _per_query_rows(self, rows, B: int) -> List[Optional[np.ndarray]]:
+        """`rows` -> per query None or an ascending, duplicate-free int64 array; the same input object gives the same array object."""
+        if rows is None:
+            return [None] * B
+        n = len(self.corpus.nodes)
+        seen: Dict[int, tuple] = {}
+
+        def norm(a):
+            hit = seen.get(id(a))
+            if hit is None:
+                arr = np.unique(np.asarray(a).reshape(-1).astype(np.int64))
+                if arr.size and (arr[0] < 0 or arr[-1] >= n):
+                    raise ValueError(f"rows must lie in [0, {n})")
+                hit = seen[id(a)] = (a, arr)               # (a is held, so its id stays its own for the call)
+            return hit[1]
+        per_query = (isinstance(rows, (list, tuple)) and len(rows) == B
+                     and all(r is None or (hasattr(r, "__len__") and not isinstance(r, (str, bytes))) for r in rows))
+        if per_query:
+            return [None if r is None else norm(r) for r in rows]
+        one = norm(rows)
+        return [one] * B
+
+    def _resolve_rows(self, dicts, rows, B: int, mode: int):
+        """Per query the rows it may rank (None: it runs through today's filter paths) and the filters left for those paths.  A query
+        with rows AND a filter keeps the rows that pass the filter (class column lookup on the host); a filter over more distinct values
+        than a class column holds becomes the rows it matches; with rows_route_max > 0 so does a filter that allows few rows."""
+        rows_q = self._per_query_rows(rows, B)
+        dicts = list(dicts)
+        corpus = self.corpus
+        exact = mode == _lib.ERH_DENSE_EXACT
+        if rows is None and not (exact and (self.rows_route_max > 0 or any(dicts))):
+            return rows_q, dicts
+        for g in _by_key_set(dicts):
+            for b in g:
+                sp = dicts[b]
+                if not sp:
+                    continue
+                keys = _spec_keys(sp)
+                if keys and exact and corpus.too_many_values(keys):
+                    allowed = corpus.rows_matching(sp)
+                    rows_q[b] = allowed if rows_q[b] is None else np.intersect1d(rows_q[b], allowed, assume_unique=True)
+                    dicts[b] = None
+                    continue
+                if rows_q[b] is None and not (exact and self.rows_route_max > 0):
+                    continue
+                # the filter as classes of the column over its keys: -1 everything, a class, a list of classes ([] nothing)
+                c = corpus.plan([sp])[0]
+                table = corpus._classes
+                if rows_q[b] is not None:
+                    r = rows_q[b]
+                    if isinstance(c, list) and not c:
+                        r = r[:0]
+                    elif c != -1:
+                        r = r[np.isin(table.ids[r], np.asarray(c if isinstance(c, list) else [c], np.int64))]
+                    rows_q[b], dicts[b] = r, None
+                elif c != -1 and not (isinstance(c, list) and not c) and c != 32767:
+                    cs = c if isinstance(c, list) else [c]
+                    if int(corpus.class_counts(table)[cs].sum()) <= self.rows_route_max:
+                        parts = [corpus.class_rows(table, int(x)) for x in cs]
+                        rows_q[b] = parts[0] if len(parts) == 1 else np.sort(np.concatenate(parts))
+                        dicts[b] = None
+        return rows_q, dicts
+
+    @staticmethod
+    def _rows_lists(rows_q: Sequence[np.ndarray]):
+        """Row arrays of the queries -> (distinct lists, list_of): identical arrays, by object identity or by content, become one list."""
+        lists: List[np.ndarray] = []
+        by_id: Dict[int, int] = {}
+        by_content: Dict[tuple, int] = {}
+        list_of = np.empty(len(rows_q), np.int32)
+        for j, r in enumerate(rows_q):
+            l = by_id.get(id(r))
+            if l is None:
+                key = (r.shape[0], r.tobytes())
+                l = by_content.get(key)
+                if l is None:
+                    l = by_content[key] = len(lists)
+                    lists.append(r)
+                by_id[id(r)] = l
+            list_of[j] = l
+        return lists, list_of
+
+    def _query_filtered(self, q, k: int, dicts, mode: int):
+        """The batch through the filter paths: class column, class sets, one device column per metadata key set."""
+        B = q.shape[0]
         groups = _by_key_set(dicts)
         has_sets = any(isinstance(sp, _SetFilter) for sp in dicts)
         if len(groups) <= 1 and not has_sets:
@@ -713,8 +871,8 @@ class HipVectorStore:
                                                                    mode=mode)
         return ids, sc, ln
 
-    def query(self, query_embedding, similarity_top_k: int, filters=None):
-        ids, sc, ln = self.query_batch(query_embedding, similarity_top_k, filters)
+    def query(self, query_embedding, similarity_top_k: int, filters=None, rows=None):
+        ids, sc, ln = self.query_batch(query_embedding, similarity_top_k, filters, rows=rows)
         n = int(ln[0])
         return [self.corpus.nodes[i] for i in ids[0, :n]], [float(s) for s in sc[0, :n]]
 
@@ -767,17 +925,49 @@ class QdrantRetriever(_RetrieverBase):
         nodes, sims = self._vector_store.query(emb, self._similarity_top_k, self.filters)
         return [NodeWithScore(node=n, score=s) for n, s in zip(nodes, sims)]
 
-    def retrieve_batch(self, queries: Sequence[str], filters=_UNSET) -> List[List[NodeWithScore]]:
+    def retrieve_batch(self, queries: Sequence[str], filters=_UNSET, rows=None) -> List[List[NodeWithScore]]:
         """`_retrieve` for a batch.  `filters` (default: the `filters` attribute, for every query) may be a list parallel to
-        `queries`: one qdrant Filter / dict / None per question, as the reference's evaluation loop sets them one at a time."""
+        `queries`: one qdrant Filter / dict / None per question, as the reference's evaluation loop sets them one at a time.
+        `rows`: HipVectorStore.query_batch's argument -- node positions a query is restricted to (one array, or one array / None each)."""
         if len(queries) == 0:
             return []
         embs = np.asarray([self._embed_model.get_query_embedding(q) for q in queries], dtype=np.float32)
         ids, sc, ln = self._vector_store.query_batch(embs, self._similarity_top_k,
-                                                     self.filters if filters is _UNSET else filters)
+                                                     self.filters if filters is _UNSET else filters, rows=rows)
         nodes = self._vector_store.nodes
         return [[NodeWithScore(node=nodes[i], score=float(s)) for i, s in zip(ids[b, :ln[b]], sc[b, :ln[b]])]
                 for b in range(len(queries))]
+
+    def score_nodes(self, query: str, nodes_or_ids, top_k: Optional[int] = None) -> List[NodeWithScore]:
+        """The given nodes -- positions in the node list, or node objects of it (NodeWithScore included) -- and nothing else, ranked by
+        the embedding: the dense twin of BM25Retriever.get_scores(query, docs).  Every node gets its exact score on the device (one
+        call, the nodes in lists of at most 768, the call's limit on k); (score desc, position asc); `top_k` cuts the result."""
+        store = self._vector_store
+        where = store.__dict__.get("_position")
+        ids = []
+        for x in nodes_or_ids:
+            if isinstance(x, (int, np.integer)):
+                ids.append(int(x))
+                continue
+            if where is None:
+                where = store.__dict__["_position"] = {id(n): i for i, n in enumerate(store.nodes)}
+            node = getattr(x, "node", x)
+            if id(node) not in where:
+                raise ValueError("score_nodes: a node that is not part of this store's node list")
+            ids.append(where[id(node)])
+        ids = np.unique(np.asarray(ids, np.int64))
+        if ids.size == 0:
+            return []
+        chunks = [ids[i:i + DENSE_MAX_K] for i in range(0, ids.size, DENSE_MAX_K)]
+        emb = np.asarray(self._embed_model.get_query_embedding(query), dtype=np.float32)
+        got, sc, ln = store.query_batch(np.tile(emb, (len(chunks), 1)), len(chunks[0]), None, rows=chunks)
+        got = np.concatenate([got[j, :ln[j]] for j in range(len(chunks))])
+        sc = np.concatenate([sc[j, :ln[j]] for j in range(len(chunks))])
+        order = np.lexsort((got, -sc))                     # (one chunk: already in this order)
+        if top_k is not None:
+            order = order[:max(int(top_k), 0)]
+        nodes = store.nodes
+        return [NodeWithScore(node=nodes[int(got[i])], score=float(sc[i])) for i in order]
 
 
 class BM25Retriever(_RetrieverBase):
@@ -1073,12 +1263,13 @@ class HybridRetriever(_RetrieverBase):
         """Route selection + filter push-down + RRF (retrievers.py:276-291)."""
         return self.retrieve_batch([query_bundle.query_str])[0]
 
-    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, filters=_UNSET) -> List[List[NodeWithScore]]:
+    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, filters=_UNSET, rows=None) -> List[List[NodeWithScore]]:
         """`_aretrieve` for a batch of query strings.  Without the keyword arguments the `filter_dict` / `filters`
         attributes apply to every query and are pushed into the child retrievers as the reference does
         (retrievers.py:278,283).  `filter_dicts` (sparse route) / `filters` (dense route) may instead be lists parallel to
         `queries` -- the reference's evaluation loop changes both before every question (pipeline.py:301-312,331-341), so a
-        batch of its questions needs one filter per query; the child retrievers' attributes are left alone then."""
+        batch of its questions needs one filter per query; the child retrievers' attributes are left alone then.
+        `rows` restricts the DENSE route (QdrantRetriever.retrieve_batch's argument); the sparse route keeps its filter_dict."""
         sp, de = self.sparse_retriever, self.dense_retriever
         B = len(queries)
         if B == 0:
@@ -1094,15 +1285,22 @@ class HybridRetriever(_RetrieverBase):
             if filters is _UNSET:
                 de.filters = self.filters
             if self.retrieval_type == 1:
-                return de.retrieve_batch(queries, filters=fdn)
+                return de.retrieve_batch(queries, filters=fdn, rows=rows)
         # filter_dict restricts the sparse route only, filters the dense route only (retrievers.py:278,283)
         d_sparse = _per_query(fs, B, lambda v: dict(v) if v else None)
         d_dense = _per_query(fdn, B, _spec_cache())
         key_sets = {_spec_keys(fd) for fd in d_sparse + d_dense if _spec_keys(fd)}
         if not self._fused_possible() or len(key_sets) > 1 or not self._fused_sizes():
             # (outside erh_hybrid_topk's sizes the routes run on their own: each one falls back or names its limit)
-            sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs), de.retrieve_batch(queries, filters=fdn)
+            sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs), de.retrieve_batch(queries, filters=fdn, rows=rows)
             return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
+        vs = de._vector_store
+        if rows is not None or any(sp and _spec_keys(sp) and vs.corpus.too_many_values(_spec_keys(sp)) for sp in d_dense):
+            rows_q, _ = vs._resolve_rows(d_dense, rows, B, _lib.ERH_DENSE_EXACT)
+            if any(r is None for r in rows_q):         # a batch that mixes rows and non-rows dense queries: the routes on their own + RRF
+                sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs), de.retrieve_batch(queries, filters=fdn, rows=rows)
+                return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
+            return self._retrieve_rows(queries, d_sparse, rows_q)
         if any(isinstance(fd, _SetFilter) for fd in d_dense):
             return self._retrieve_sets(queries, d_sparse, d_dense)
         # both routes share one engine: BM25 -> dense -> RRF([sparse, dense]) in a single device pipeline, one class column
@@ -1133,6 +1331,26 @@ class HybridRetriever(_RetrieverBase):
         dids, _, dln = eng.dense_topk_sets(embs, de._similarity_top_k,
                                            [None if c == -1 else (c if isinstance(c, list) else [c]) for c in plan], device_out=True)
         eng.dense_check()
+        fids, fsc, fln = eng.rrf_device(sids, sln, dids, dln, K=60, topk=self.topk)
+        eng.sync()
+        ids, sc, ln = fids.cpu().numpy(), fsc.cpu().numpy(), fln.cpu().numpy()
+        nodes = sp._nodes
+        return [[NodeWithScore(node=nodes[i], score=float(s)) for i, s in zip(ids[b, :ln[b]], sc[b, :ln[b]])]
+                for b in range(B)]
+
+    def _retrieve_rows(self, queries: Sequence[str], d_sparse, rows_q) -> List[List[NodeWithScore]]:
+        """retrieval_type 3 with explicit rows on the dense side, every step on the device: BM25 top-k (class column of filter_dict) and
+        erh_dense_topk_rows into device buffers, the RRF kernel over the two device lists, one synchronisation (the rows entry leaves
+        nothing for erh_dense_check)."""
+        sp, de = self.sparse_retriever, self.dense_retriever
+        eng, cstate = sp.engine, sp._corpus_state
+        B = len(queries)
+        filt_s = cstate.filter_column(d_sparse)
+        lists, list_of = de._vector_store._rows_lists(rows_q)
+        qi, qt = queries_to_csr([sp._query_ids(q) for q in queries])
+        embs = _unit_f16(np.asarray([de._embed_model.get_query_embedding(q) for q in queries], dtype=np.float32))
+        sids, _, sln = eng.bm25_topk(qi, qt, sp._similarity_top_k, filter_dir=filt_s, device_out=True, slot=sp._slot)
+        dids, _, dln = eng.dense_topk_rows(embs, de._similarity_top_k, lists, list_of=list_of, device_out=True)
         fids, fsc, fln = eng.rrf_device(sids, sln, dids, dln, K=60, topk=self.topk)
         eng.sync()
         ids, sc, ln = fids.cpu().numpy(), fsc.cpu().numpy(), fln.cpu().numpy()

@@ -32,6 +32,8 @@
  *   erh_dense_topk       QdrantRetriever._aretrieve / _retrieve (retrievers.py:37-69)
  *   erh_dense_topk_sets  the same with any Qdrant payload filter over the class column's keys (retrievers.py:44-47 hands
  *                        QdrantRetriever.filters to Qdrant unchanged: MatchAny, MatchExcept, should, must_not, Range)
+ *   erh_dense_topk_rows  the same restricted to a point-id set per query (a HasIdCondition beside the filter Qdrant gets from
+ *                        retrievers.py:44-47): explicit row lists, exact by scoring every listed row
  *   erh_bm25_scores      BM25Retriever.get_scores (retrievers.py:128-151)
  *   erh_bm25_topk        BM25Retriever._retrieve = get_scores + filter (retrievers.py:191-220)
  *   erh_rrf              HybridRetriever.reciprocal_rank_fusion (retrievers.py:256-274)
@@ -219,6 +221,27 @@ int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, i
  * over the call's sub-queries. */
 int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
                         int B, int k, const int32_t *set_ptr, const int16_t *set_cls, int mode,
+                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
+
+/* Dense top-k where each query ranks an EXPLICIT LIST OF ROWS and nothing else: what a Qdrant search restricted to a point-id set returns
+ * (the reference's QdrantRetriever hands its filter to Qdrant unchanged, src/easyrag/custom/retrievers.py:44-47; an id set is one more
+ * condition there) -- a candidate list to re-score, an ACL's ids, a session's ids, a dir of a few hundred chunks -- and the dense twin of
+ * BM25Retriever.get_scores(query, docs).
+ *   list_ptr int64[n_lists+1], list_rows int32[list_ptr[n_lists]] (host CSR): list l = list_rows[list_ptr[l] .. list_ptr[l+1]), row ids in the
+ *   caller's numbering, strictly ascending, in [0, N); list_ptr[0] = 0, non-decreasing.  list_of host int32[B]: the list of query b, -1 = no rows
+ *   (out_len[b] = 0); any number of queries may name the same list (they then share its row loads where the list is long).  Anything else:
+ *   ERH_ERR_INVALID, checked on the host before anything is enqueued (outputs untouched).  k outside [1, 768]: ERH_ERR_UNSUPPORTED; no chunk
+ *   matrix: ERH_ERR_STATE; work space that cannot be allocated: ERH_ERR_NOMEM.
+ * Ranking: ERH_DENSE_EXACT's, and only that -- every listed row gets its pinned-order fp64 score, so there is no threshold, no candidate
+ * budget and no mode.  Result for query b: the first k of its rows under (score descending, row id ascending), padded like every other
+ * entry (id -1, score 0); out_len[b] = min(k, length of its list).
+ * Host outputs are final on return, device outputs after a stream synchronisation (erh_sync).  The call sets no flag words: it needs no
+ * erh_dense_check, a check behind it does nothing on its account (it still finishes an earlier dense call that waits for one -- a rows call
+ * may sit between such a call and its check), and erh_dense_diag / erh_dense_exhaustive_count, which describe scan-route calls, count no query of it.
+ * Option dense_rows_ws_mb (256): score work space of lists longer than 2048 rows, at least one list of N rows; a call that needs more runs in
+ * chunks of queries. */
+int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q, int B, int k,
+                        int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
                         int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
 
 /* BM25 top-k.  Queries as CSR of term ids (host): q_indptr int32[B+1], q_tok int32[q_indptr[B]].
@@ -465,6 +488,9 @@ int erh_dense_exhaustive_count(erh_handle *h, int32_t *count);
  *   dense_grouped_launches                             calls whose block groups ran as one launch per stage (dense_group_launch)
  *   dense_candidates_last_call                         candidates the last dense pipeline's scan handed to its final kernel, summed over
  *                                                      its queries (read back from the device: synchronises; not reset by erh_reset_stats)
+ *   dense_rows_calls                                   erh_dense_topk_rows calls
+ *   dense_rows_short_launches / dense_rows_long_launches  its launches of the short shape (one workgroup per query, lists of at most 2048 rows) /
+ *                                                      of the long shape (one score + select pair per chunk of queries)
  *   bm25_mixed_launches                                BM25 scans launched with both bodies (bm25_mixed: a batch with queries longer than bm25_long_tokens)
  *   bm25_redo_segments                                 (query, segment) pairs the fixed-point scan handed to the exact block scan (device counter)
  * Reading a device counter synchronises the device.  Unknown name: ERH_ERR_INVALID. */
