@@ -232,7 +232,8 @@ int erh_get_stat(erh_handle *h, const char *name, int64_t *value) {
         {"dense_sample_passes", T.dense_sample_passes}, {"dense_tile384_nomem", T.dense_tile384_nomem},
         {"bm25_calls", T.bm25_calls}, {"hybrid_calls", T.hybrid_calls}, {"dense_block_groups", T.dense_block_groups},
         {"dense_grouped_launches", T.dense_grouped_launches}, {"bm25_mixed_launches", T.bm25_mixed_launches},
-        {"dense_rows_calls", T.dense_rows_calls}, {"dense_rows_short_launches", T.dense_rows_short}, {"dense_rows_long_launches", T.dense_rows_long}};
+        {"dense_rows_calls", T.dense_rows_calls}, {"dense_rows_short_launches", T.dense_rows_short}, {"dense_rows_long_launches", T.dense_rows_long},
+        {"dense_group_reruns", T.dense_group_reruns}};
     for (const auto &e : host)
         if (!strcmp(name, e.n)) { *value = e.v; return ERH_OK; }
     if (!strcmp(name, "dense_candidates_last_call")) {
@@ -333,6 +334,12 @@ int erh_set_dense(erh_handle *h, const void *x, int64_t n, int d, int dtype, int
     float xn = 0.f;
     HIPCHK(h, hipMemcpyAsync(&xn, h->flags.p, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
+    // The norm went through the flag words, and the matrix the last dense call scanned is gone: nothing of that call is left for
+    // erh_dense_check to read (it would take the norm's bits for a flagged query and the old matrix for the exhaustive path's).
+    h->last = erh_handle::LastDense();
+    h->routed.done = false; h->routed.pending = false;
+    h->sets.on = false;
+    h->qstate = erh_handle::QueryState();
     h->xnorm_max = xn;
     h->N = n;
     h->d = d;
@@ -1479,6 +1486,35 @@ int erh_debug_dense_scores(erh_handle *h, const void *q_f16_host, int B, int64_t
         HIPCHK(h, hipMemcpyAsync(out, h->S0.p, (size_t)B * rows * 4, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(h, hipStreamSynchronize(st));
+    return ERH_OK;
+}
+
+int erh_debug_dense_query_state(erh_handle *h, float *tau, uint32_t *cand_cnt, uint32_t *flag, int B) {
+    if (!h) return ERH_ERR_INVALID;
+    if (!tau || !cand_cnt || !flag || B <= 0) return h->fail(ERH_ERR_INVALID, "erh_debug_dense_query_state: null pointer or empty batch");
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());
+    erh_handle::QueryState &S = h->qstate;
+    const size_t n = (size_t)std::max(S.rows, 0);
+    std::vector<float> t_dev;
+    std::vector<uint32_t> c_dev, f_dev;
+    const float *t = S.tau.data();
+    const uint32_t *c = S.cnt.data(), *f = S.flag.data();
+    if (!S.snap) {                                                     // no re-run since the pipeline: its words are still in the work space
+        t_dev.resize(n); c_dev.resize(n); f_dev.resize(n);
+        if (n) {
+            HIPCHK(h, hipMemcpy(t_dev.data(), h->tau.p, n * 4, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(c_dev.data(), h->cand_cnt.p, n * 4, hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(f_dev.data(), h->bad.p, n * 4, hipMemcpyDeviceToHost));
+        }
+        t = t_dev.data(); c = c_dev.data(); f = f_dev.data();
+    }
+    for (int i = 0; i < B; ++i) { tau[i] = NAN; cand_cnt[i] = 0xffffffffu; flag[i] = 0u; }
+    for (size_t r = 0; r < n; ++r) {
+        const int64_t q = S.src.empty() ? (int64_t)r : (r < S.src.size() ? (int64_t)S.src[r] : -1);
+        if (q < 0 || q >= B) continue;
+        tau[q] = t[r]; cand_cnt[q] = c[r]; flag[q] = f[r];
+    }
     return ERH_OK;
 }
 

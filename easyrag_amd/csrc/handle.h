@@ -125,6 +125,15 @@ struct erh_handle {
     // a routed group run as a pipeline of its own writes its lists straight to the caller's rows, block rows mapped to document ids
     // (dense_finalize_kernel: ErhGroupIo::row_map / id_map / single_lo) -- set around that dense_topk_dev call only
     struct ViewOut { bool on = false; const int32_t *id_map = nullptr; int32_t id_lo = 0; const int32_t *row_map = nullptr; } view_out;
+    // erh_debug_dense_query_state: which rows of tau / cand_cnt / bad the LAST dense pipeline of the last call used and whose they are.
+    // A group run again at the check goes through the same work space: the words are copied aside (snap) before the first re-run.
+    struct QueryState {
+        int rows = 0;                      // pipeline rows (the grouped launch: its padded block)
+        std::vector<int32_t> src;          // caller row of every pipeline row, -1 = padding; empty: row i is query i
+        bool snap = false;
+        std::vector<float> tau;
+        std::vector<uint32_t> cnt, flag;
+    } qstate;
     int cand_rows = 0;                    // query rows of cand_cnt the last dense pipeline used (erh_get_stat: dense_candidates_last_call)
     bool rerun = false;                   // dense_topk_dev is re-running a group of a routed call at its check: its flagged queries were counted already
     int opt_bm25_small = 2;               // fixed-point scan, when k allows: 2 the 512-thread shape with packed 16-bit sums over 32768-document
@@ -235,7 +244,8 @@ struct erh_handle {
     struct Stats {
         int64_t dense_calls = 0, dense_scan_pp5 = 0, dense_scan_pp3 = 0, dense_scan_gemv = 0, dense_scan_tile = 0,
                 dense_sample_passes = 0, dense_tile384_nomem = 0, bm25_calls = 0, hybrid_calls = 0, dense_block_groups = 0,
-                dense_grouped_launches = 0, bm25_mixed_launches = 0, dense_rows_calls = 0, dense_rows_short = 0, dense_rows_long = 0;
+                dense_grouped_launches = 0, bm25_mixed_launches = 0, dense_rows_calls = 0, dense_rows_short = 0, dense_rows_long = 0,
+                dense_group_reruns = 0;
     } stats;
     // multi-GPU exchange (erh_comm_* / erh_allgather_topk): RCCL communicator + packed send / receive rows
     void *comm = nullptr;

@@ -110,6 +110,11 @@ hipError_t launch_dense_gemv_store(const _Float16 *X, int64_t N, int d, int64_t 
 constexpr int kDenseN0Max = 32768;    // longest seed prefix (one fp32 score row per query in S0; until round 6 it also had to fit LDS for the full-sort fall-back)
 constexpr int kDenseCapMax = 16384;   // candidates per query that the LDS sort can hold (64-bit keys)
 constexpr int kDenseRescoreMax = 1024;
+// Why a query was flagged in bad[q] (OR-ed; every consumer tests != 0; erh_debug_dense_query_state reports the word)
+constexpr uint32_t kDenseBadList = 1u;          // candidate list overflow (seed select, refine, appends beyond the capacity)
+constexpr uint32_t kDenseBadGather = 2u;        // the final kernel's gather exceeds 2048 entries
+constexpr uint32_t kDenseBadRescore = 4u;       // re-score set cut, or fp32 error above delta
+constexpr uint32_t kDenseBadSpeculation = 8u;   // speculative threshold not verified
 hipError_t select_init();
 // fp32/fp16 -> fp16 query block [Bpad x d] (+ fp32 norm of the fp16 row); rows >= B are zeroed.
 hipError_t launch_prep_queries(const void *q, int q_dtype, int normalize, int B, int Bpad, int d,

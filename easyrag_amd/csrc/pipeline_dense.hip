@@ -270,6 +270,7 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
               HIPCHK(h, erh::launch_dense_exhaustive(bad, B, 0, k, X, N, d, Q16, filter_dev,
                                                      (filter_dev && h->has_dir) ? h->dir_id.as<int16_t>() : nullptr, pos_inv, h->ex_ws.p,
                                                      flags, h->n_cus, d_ids, d_sc, d_len, h->rerun ? nullptr : h->dstats.as<unsigned long long>(), 1 /* count only */, st)); }
+            if (!h->rerun) { h->qstate.rows = B; h->qstate.src.clear(); h->qstate.snap = false; }
             h->last = erh_handle::LastDense();
             h->last.valid = true;
             h->last.B = B; h->last.k = k; h->last.filter_dev = filter_dev; h->last.X = X; h->last.N = N; h->last.pos_inv = pos_inv;
@@ -366,6 +367,7 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
       HIPCHK(h, erh::launch_dense_exhaustive(bad, B, 0, k, X, N, d, Q16, filter_dev,
                                              (filter_dev && h->has_dir) ? h->dir_id.as<int16_t>() : nullptr, pos_inv, h->ex_ws.p,
                                              flags, h->n_cus, d_ids, d_sc, d_len, h->rerun ? nullptr : h->dstats.as<unsigned long long>(), 1 /* count only */, st)); }
+    if (!h->rerun) { h->qstate.rows = B; h->qstate.src.clear(); h->qstate.snap = false; }
     h->last = erh_handle::LastDense();
     h->last.valid = true;
     h->last.B = B; h->last.k = k; h->last.filter_dev = filter_dev; h->last.X = X; h->last.N = N; h->last.pos_inv = pos_inv;
@@ -437,6 +439,19 @@ int dense_check_flags(erh_handle *h, hipStream_t st) {
             } else {
                 q_rows = h->r_q.as<char>() + (size_t)g.at * row_bytes;
             }
+            if (!h->qstate.snap) {                                     // the last pipeline's per-query words, before a re-run overwrites them
+                erh_handle::QueryState &S = h->qstate;
+                const size_t n = (size_t)std::max(S.rows, 0);
+                S.tau.resize(n); S.cnt.resize(n); S.flag.resize(n);
+                if (n) {
+                    HIPCHK(h, hipMemcpyAsync(S.tau.data(), h->tau.p, n * 4, hipMemcpyDeviceToHost, st));
+                    HIPCHK(h, hipMemcpyAsync(S.cnt.data(), h->cand_cnt.p, n * 4, hipMemcpyDeviceToHost, st));
+                    HIPCHK(h, hipMemcpyAsync(S.flag.data(), h->bad.p, n * 4, hipMemcpyDeviceToHost, st));
+                    HIPCHK(h, hipStreamSynchronize(st));
+                }
+                S.snap = true;
+            }
+            h->stats.dense_group_reruns += 1;
             h->rerun = true;
             int rc = routed_group_run(h, g, q_rows, dt, nq, st);       // (clears routed.done: the check below is the ordinary one)
             if (rc == ERH_OK) rc = dense_check_flags(h, st);
@@ -515,6 +530,7 @@ static int routed_group_run(erh_handle *h, const erh_handle::RoutedGroup &g, con
                                   direct ? R.d_len : h->r_len.as<int32_t>(), st);
     h->view_out = erh_handle::ViewOut();
     h->view_global();
+    if (direct && rc == ERH_OK) h->qstate.src.assign(h->r_idx_host.begin() + g.at, h->r_idx_host.begin() + g.at + g.n);
     return rc;
 }
 
@@ -689,6 +705,7 @@ static int dense_topk_grouped(erh_handle *h, const void *q_dev, int q_dtype, int
       HIPCHK(h, erh::launch_dense_exhaustive(bad, Bpad, 0, k, nullptr, P.n_max, d, h->Q16.as<_Float16>(), nullptr, nullptr, 1, h->ex_ws.p,
                                              flags, h->n_cus, d_ids, d_sc, d_len, h->dstats.as<unsigned long long>(), 1 /* count only */, st)); }
     h->stats.dense_grouped_launches += 1;
+    h->qstate.rows = Bpad; h->qstate.src = P.q_src; h->qstate.snap = false;
     return ERH_OK;
 }
 

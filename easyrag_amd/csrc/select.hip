@@ -211,7 +211,7 @@ __device__ __forceinline__ void seed_emit(const float *__restrict__ row, int n0,
     if (tid == 0) {
         const int c = *s_cnt;
         cand_cnt[q] = (uint32_t)(c < cap ? c : cap);
-        if (c > cap) bad[q] = 1u;                        // list too short for this query: the exhaustive path answers it
+        if (c > cap) atomicOr(&bad[q], erh::kDenseBadList);   // list too short for this query: the exhaustive path answers it
     }
 }
 
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(kSelThreads) void seed_select_kernel(
                 if (tid == 0) {
                     tau[q] = prune;
                     cand_cnt[q] = (uint32_t)(m < cap ? m : cap);
-                    if (m > cap) bad[q] = 1u;
+                    if (m > cap) atomicOr(&bad[q], erh::kDenseBadList);
                 }
                 return;
             }
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(kSelThreads) void cand_refine_kernel(
     const int q = blockIdx.x, tid = threadIdx.x;
     int c = (int)cand_cnt[q];
     if (c > cap) {                                         // appends were dropped in the stage before this boundary
-        if (threadIdx.x == 0 && hi_incl >= cap) bad[q] = 1u;
+        if (threadIdx.x == 0 && hi_incl >= cap) atomicOr(&bad[q], erh::kDenseBadList);
         c = cap;
     }
     if (c <= lo_excl || c > hi_incl) return;               // the other launch's query (uniform)
@@ -527,6 +527,7 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
         if ((q & 255) >= v.nq) return;                                  // a padding row
         X = v.X; N = v.N; pos_mul = v.mul; pos_inv = v.inv; id_lo = v.id_lo;
         out_row = gio.q_src[q];
+        if (v.rank >= k) tau = nullptr;                                 // this view's threshold is a guaranteed bound: nothing to verify
     } else {                                                            // one view for the launch: rows / ids of a routed group
         if (gio.row_map) out_row = gio.row_map[q];
         id_lo = gio.single_lo;
@@ -534,7 +535,7 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
     const int32_t *const id_map = gio.id_map;
     int c = (int)cand_cnt[q];
     if (c > cap) {                                                      // appends were dropped: not answerable from the list
-        if (tid == 0 && lead) bad[q] = 1u;
+        if (tid == 0 && lead) atomicOr(&bad[q], erh::kDenseBadList);
         c = cap;
     }
     const ErhCand *mine = cand + (int64_t)q * cap;
@@ -573,7 +574,7 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
         if ((tid & 63) == 0 && n_lvl) atomicAdd(&s_lvl, n_lvl);
     }
     erh_bitonic_desc<uint32_t>(tmax, kFinSlots);                        // begins and ends with a barrier
-    if (tau && tid == 0 && lead && lvl > -INFINITY && s_lvl < k) bad[q] = 1u;   // the speculation failed: exhaustive path
+    if (tau && tid == 0 && lead && lvl > -INFINITY && s_lvl < k) atomicOr(&bad[q], erh::kDenseBadSpeculation);   // the speculation failed: exhaustive path
     float gather_thr = -INFINITY;
     if (kk <= kFinSlots && tmax[kk - 1] != 0u) gather_thr = erh_ord2f(tmax[kk - 1]) - ((mode == 1) ? 0.f : 2.0f * delta);
     for (int i = tid; i < c; i += kFinThreads) {
@@ -586,7 +587,7 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
     __syncthreads();
     int g = s_cnt;
     if (g > kFinBuf) {                                                  // uniform; pathological tie clusters only
-        if (tid == 0 && lead) { bad[q] = 1u; atomicAdd(diag_uncert, 1u); }
+        if (tid == 0 && lead) { atomicOr(&bad[q], erh::kDenseBadGather); atomicAdd(diag_uncert, 1u); }
         g = kFinBuf;
     }
     const int ns = erh_next_pow2(g < 2 ? 2 : g);
@@ -743,7 +744,7 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
     if (tid == 0) {
         const float me = __uint_as_float(s_maxerr);
         atomicMax((unsigned int *)diag_maxerr, __float_as_uint(me));
-        if (uncertified || me > delta) { atomicAdd(diag_uncert, 1u); bad[q] = 1u; }   // re-score set cut, or the error bound failed
+        if (uncertified || me > delta) { atomicAdd(diag_uncert, 1u); atomicOr(&bad[q], erh::kDenseBadRescore); }   // re-score set cut, or the error bound failed
     }
 }
 

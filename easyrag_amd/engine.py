@@ -604,7 +604,7 @@ class RetrievalEngine:
     STAT_NAMES = ("dense_calls", "bm25_calls", "hybrid_calls", "dense_scan_pp5_launches", "dense_scan_pp3_launches",
                   "dense_scan_gemv_launches", "dense_scan_tile_launches", "dense_sample_passes", "dense_tile384_nomem",
                   "dense_exhaustive_queries", "bm25_redo_segments", "dense_block_groups", "dense_grouped_launches", "bm25_mixed_launches",
-                  "dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches")
+                  "dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches", "dense_group_reruns")
 
     def stat(self, name: str) -> int:
         """One counter of erh_get_stat (which kernels answered the calls since the last reset_stats)."""
@@ -629,3 +629,12 @@ class RetrievalEngine:
         self._check(self._lib.erh_debug_dense_scores(self._h, _ptr(q16), B, int(row0), int(rows),
                                                      1 if use_mfma else 0, _ptr(out)))
         return out
+
+    def dense_query_state(self, B: int):
+        """Pruning state of the last dense pipeline of the last call, per query in the caller's order (erh_debug_dense_query_state):
+        tau float32[B], cand_cnt uint32[B], flag uint32[B] (reason bits; 0 = answered by the pruned pipeline).  Synchronises."""
+        tau = np.empty(B, np.float32)
+        cnt = np.empty(B, np.uint32)
+        flag = np.empty(B, np.uint32)
+        self._check(self._lib.erh_debug_dense_query_state(self._h, _ptr(tau), _ptr(cnt), _ptr(flag), int(B)))
+        return tau, cnt, flag

@@ -486,6 +486,8 @@ int erh_dense_exhaustive_count(erh_handle *h, int32_t *count);
  *   dense_exhaustive_queries                           queries answered by the exhaustive path (device counter; summed over calls)
  *   dense_block_groups                                 query groups answered from their dir's block (dense_dir_blocks)
  *   dense_grouped_launches                             calls whose block groups ran as one launch per stage (dense_group_launch)
+ *   dense_group_reruns                                 block groups of routed calls that erh_dense_check / a host-output return ran again as pipelines of
+ *                                                      their own because one of their queries was flagged (normally 0)
  *   dense_candidates_last_call                         candidates the last dense pipeline's scan handed to its final kernel, summed over
  *                                                      its queries (read back from the device: synchronises; not reset by erh_reset_stats)
  *   dense_rows_calls                                   erh_dense_topk_rows calls
@@ -508,6 +510,16 @@ int erh_dense_seed_rank(int k, int64_t n0, int64_t n);
  * matrix, out float32[B*rows] on the host; and the MFMA scores of the same block. */
 int erh_debug_dense_scores(erh_handle *h, const void *q_f16_host, int B, int64_t row0, int rows,
                            int use_mfma, float *out);
+
+/* Debug: the pruning state of the last dense pipeline of the last dense / hybrid call, per query in the caller's order (host arrays of B
+ * entries), as of the end of that pipeline's final kernel -- exhaustive rounds and groups run again at the check do not change it.
+ *   tau       the pruning threshold the scan compared fp32 scores with
+ *   cand_cnt  entries the scan left in the query's candidate list (a count above 16384 means appends were dropped)
+ *   flag      0, or why the query was handed to the exhaustive path (OR-ed): 1 candidate list overflow, 2 gather over 2048 entries,
+ *             4 re-score set cut or fp32 error above delta, 8 speculative threshold not verified
+ * Covers an unrouted call and, of a call routed by dir block, its last pipeline (the grouped launch when there was one; its padded rows are
+ * mapped back to the caller's).  A query that pipeline did not hold gets tau = NaN, cand_cnt = 0xffffffff, flag = 0.  Synchronises the device. */
+int erh_debug_dense_query_state(erh_handle *h, float *tau, uint32_t *cand_cnt, uint32_t *flag, int B);
 
 #ifdef __cplusplus
 }

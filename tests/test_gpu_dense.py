@@ -6,54 +6,50 @@ ids and fp64 scores bit-identical to oracle.dense_exact_topk (pinned summation o
 import numpy as np
 import pytest
 
+from dense_pruning_util import (FLAG_LIST, SCAN_ARM_IDS, SCAN_ARMS, apply_scan_arm, bands, check_fast_ranking, comfortable, delta_hat,
+                                delta_of, exact_scores, reset_scan_arm, speculative)
 from easyrag_amd import _lib, synth
 from oracle import dense_exact_scores, dense_exact_topk, qdrant_cosine_search, to_f16_unit
 
 pytestmark = pytest.mark.gpu
 
 
-# (dense_cfg, dense_persist, dense_pp, dense_gemv, dense_speculate, dense_tiled)
-@pytest.fixture(params=[(0, 1, 3, 0, 1, 0), (0, 1, 3, 0, 1, 1), (0, 1, 3, 0, 0, 0), (0, 0, 0, 0, 1, 0), (0, 0, 0, 0, 0, 0),
-                        (1, 0, 0, 0, 1, 0), (2, 0, 0, 0, 0, 0), (0, 1, 3, 1, 1, 1)],
-                ids=["pingpong-strict-rowmajor-256x256x32", "pingpong-strict-tiled-256x256x32", "pingpong-strict-rowmajor-guaranteed-bounds",
-                     "cfg0-256x256x64-per-tile", "cfg0-per-tile-guaranteed-bounds", "cfg1-128x256x32-per-tile",
-                     "cfg2-256x256x32-per-tile-guaranteed-bounds", "gemv-16x16x32-up-to-64-queries"])
+@pytest.fixture(params=SCAN_ARMS, ids=SCAN_ARM_IDS)
 def scan_cfg(request, engine):
     """Every dense-scan kernel of the product library (the strict ping-pong scan, the per-tile fallbacks in their three tile
     configurations, the skinny-GEMM stream) / chunk layout must satisfy every parity test, with
     the speculative (verified) first threshold and with guaranteed bounds refined in stages.  The last arm lets batches of
     at most 64 queries take the skinny-GEMM stream in 1 / 2 / 4 column groups of 16 (larger batches use the ping-pong scan); the other arms pin the padded
-    256-query scans for every batch size.  (dense_tiled takes effect at the next set_dense: every test sets its own.)"""
-    engine.set_option("dense_cfg", request.param[0])
-    engine.set_option("dense_persist", request.param[1])
-    engine.set_option("dense_pp", request.param[2])
-    engine.set_option("dense_gemv", request.param[3])
-    engine.set_option("dense_speculate", request.param[4])
-    engine.set_option("dense_tiled", request.param[5])
+    256-query scans for every batch size.  (dense_tiled takes effect at the next set_dense: every test sets its own.)
+    The arm list lives in dense_pruning_util.py (the pruning tests use it too)."""
+    apply_scan_arm(engine, request.param)
     yield request.param
-    engine.set_option("dense_cfg", 0)
-    engine.set_option("dense_persist", 1)
-    engine.set_option("dense_pp", 3)
-    engine.set_option("dense_gemv", 1)
-    engine.set_option("dense_speculate", 1)
-    engine.set_option("dense_tiled", 0)
+    reset_scan_arm(engine)
 
 
 def test_mfma_scores_match_plain_gpu_and_numpy(engine, scan_cfg):
+    """fp32 scores of the store kernel (MFMA) and of the plain kernel against fp64, within dh = 1.01 * d * 2^-23 * |q| * max|x| per query --
+    DESIGN's bound, which the pruning margins rest on (1e-4 against an fp32 product, the earlier tolerance, is 6 x looser at d = 128 and
+    would not see a dropped fragment at d = 3584).  d = 64 (two K-steps), 128, 1024 and the reference's 3584."""
     # asymmetric operands: a swapped C/D layout or a wrong swizzle cannot pass
     rng = np.random.default_rng(11)
-    n, d, b = 1000, 128, 70
-    x = to_f16_unit(rng.standard_normal((n, d)) * np.linspace(0.2, 3.0, d))
-    q = to_f16_unit(rng.standard_normal((b, d)) + 0.5)
-    engine.set_dense(x)
-    ref = x.astype(np.float32) @ q.astype(np.float32).T          # [n, b]
-    for row0, rows in ((0, 1000), (37, 300), (999, 1)):
-        naive = engine.debug_dense_scores(q, row0, rows, use_mfma=False)
-        mfma = engine.debug_dense_scores(q, row0, rows, use_mfma=True)
-        want = ref[row0:row0 + rows].T
-        assert np.max(np.abs(naive - want)) < 1e-4
-        assert np.max(np.abs(mfma - want)) < 1e-4
-        assert np.max(np.abs(mfma - naive)) < 1e-4
+    n, b = 1000, 70
+    for d in (128, 64, 1024, 3584):
+        x = to_f16_unit(rng.standard_normal((n, d)) * np.linspace(0.2, 3.0, d))
+        q = to_f16_unit(rng.standard_normal((b, d)) + 0.5)
+        engine.set_dense(x)
+        ref = exact_scores(x, q)                                      # [b, n] fp64
+        dh = delta_hat(x, q)[:, None]
+        assert d > 128 or np.all(2.0 * dh < 1e-4)                     # (the earlier tolerance, implied)
+        for row0, rows in ((0, 1000), (37, 300), (999, 1)):
+            naive = engine.debug_dense_scores(q, row0, rows, use_mfma=False)
+            mfma = engine.debug_dense_scores(q, row0, rows, use_mfma=True)
+            want = ref[:, row0:row0 + rows]
+            e_naive, e_mfma = np.abs(naive - want), np.abs(mfma - want)
+            print(f"d={d} rows {row0}+{rows}: max |naive - fp64| {e_naive.max():.3g}, max |mfma - fp64| {e_mfma.max():.3g}, dh {dh.min():.3g}")
+            assert np.all(e_naive <= dh), (d, row0, float(np.max(e_naive / dh)))
+            assert np.all(e_mfma <= dh), (d, row0, float(np.max(e_mfma / dh)))
+            assert np.all(np.abs(mfma.astype(np.float64) - naive) <= 2.0 * dh), (d, row0)
 
 
 CASES = [
@@ -111,15 +107,31 @@ def test_dense_topk_exact_matches_oracle(engine, scan_cfg, n, d, b, k, n0, n1):
     engine.set_option("dense_n1", n1)
     try:
         ids, sc, ln = engine.dense_topk(q16, k, mode=_lib.ERH_DENSE_EXACT)
+        diag = engine.dense_diag()
+        tau, cnt, flag = engine.dense_query_state(b)                 # the pruning state of the EXACT call
         fids, fsc, fln = engine.dense_topk(q16, k, mode=_lib.ERH_DENSE_FAST)
     finally:
         engine.set_option("dense_n0", 32768)
         engine.set_option("dense_n1", 131072)
-    diag = engine.dense_diag()
     assert diag["uncertified"] == 0 and diag["max_abs_err"] <= diag["margin"]
     kk = min(k, n)
     assert np.all(ln == kk) and np.all(fln == kk)
     check = sorted(set(list(range(min(b, 6))) + list(range(0, b, max(1, b // 10))) + [b - 1, min(b - 1, 256)]))
+    # Pruning, not only answers (dense_pruning_util.py): the full fp64 score vector of every sampled query, shared by the eight arms.
+    # A comfortable query -- list, gather and re-score set provably inside their budgets, threshold guaranteed or provably verifiable --
+    # must not be flagged.  With guaranteed bounds refined in stages (dense_speculate = 0 and a boundary n0 < n1 < n) the device's tau is
+    # the LAST stage's: it bounds the final list, the gather and the re-score set, but not the list of an earlier, looser stage, so the
+    # list-overflow bit is left out there.  ERH_DENSE_FAST is checked as a ranking against the same scores.
+    e_rows, dl = _oracle_cached("scores", case, -1, lambda: (exact_scores(x, q16[check]), delta_of(x, q16[check])))
+    spec = bool(scan_cfg[4]) and speculative(k, n0, n)
+    staged = not spec and n0 < n1 < n
+    for j, i in enumerate(check):
+        bd = bands(e_rows[j], tau[i], dl[j], k)
+        if comfortable(bd, k, spec):
+            assert (int(flag[i]) & ~(FLAG_LIST if staged else 0)) == 0, f"query {i}: flagged {flag[i]} although comfortable: tau {tau[i]!r} cand_cnt {cnt[i]} {bd}"
+        if not staged and cnt[i] <= 16384:
+            assert bd["L"] <= cnt[i] <= bd["U"], f"query {i}: tau {tau[i]!r} cand_cnt {cnt[i]} {bd}"
+        check_fast_ranking(fids[i, :kk], fsc[i, :kk], e_rows[j], None, k, bd["dh"], what=f"query {i} (FAST)")
     for i in check:                                   # the oracle is O(n*d) fp64 per query: sample large batches
         oid, osc = _oracle_cached("exact", case, i, lambda: dense_exact_topk(x, q16[i], k))
         assert ln[i] == kk and fln[i] == kk
@@ -551,6 +563,21 @@ def test_dense_device_resident_inputs_all_dtypes(engine):
     for i in (0, 6):
         oid, osc = dense_exact_topk(x16, q16[i], 25)
         assert np.array_equal(got[0][i], oid) and np.array_equal(got[1][i].view(np.uint64), osc.view(np.uint64))
+
+
+def test_dense_check_behind_a_new_matrix(engine):
+    """erh_set_dense computes the largest row norm through the handle's flag words.  A check behind it (nothing dense has run on the new
+    matrix) must not take those bits for a flagged query of the call before -- an ordinary, unrouted one, whose matrix is gone."""
+    x = synth.dense_corpus(3000, 64, seed=5)
+    q16 = to_f16_unit(synth.dense_queries(x, 4, seed=6))
+    engine.set_dense(x)
+    ids, sc, ln = engine.dense_topk(q16, 10)
+    engine.set_dense(synth.dense_corpus(2000, 128, seed=7))
+    engine.dense_check()
+    engine.set_dense(x)
+    again = engine.dense_topk(q16, 10)
+    assert np.array_equal(ids, again[0]) and np.array_equal(sc.view(np.uint64), again[1].view(np.uint64))
+    assert engine.dense_diag()["exhaustive"] == 0
 
 
 def test_dense_errors(engine):

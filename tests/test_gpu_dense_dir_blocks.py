@@ -181,9 +181,12 @@ def test_blocks_exhaustive_path_inside_a_block(blocks_opts):
     filt = np.array([1, 1, 1, 0, 2, 1, -1, 0, 2], np.int16)
     engine.set_dense(x)
     engine.set_doc_meta(n, None, dir_id)
+    engine.reset_stats()
     routed = engine.dense_topk(q16, k, filter_dir=filt)
     diag = engine.dense_diag()
     assert diag["uncertified"] == 0 and diag["exhaustive"] >= 4    # the four queries of dir 1 at least (the unfiltered one sees the ties too)
+    if engine.group_launch:
+        assert engine.stat("dense_group_reruns") >= 1              # the re-run of a flagged group of the grouped launch DID run
     ids, sc, ln = routed
     for i in np.flatnonzero(filt == 1):
         assert np.array_equal(ids[i], np.arange(5000, 5000 + k))   # all ties: lowest ids of the block
@@ -370,6 +373,8 @@ def test_grouped_launch_tile_shapes(engine):
         st, diag = engine.stats(), engine.dense_diag()
         assert st["dense_block_groups"] == 7 and st["dense_grouped_launches"] == 1 and diag["uncertified"] == 0, (st, diag)
         assert diag["exhaustive"] == 0 and diag["max_abs_err"] <= diag["margin"]
+        # (after a routed call diag["exhaustive"] is summed over the RE-RUNS: it stays 0 while whole groups run twice; these two do not)
+        assert st["dense_exhaustive_queries"] == 0 and st["dense_group_reruns"] == 0, st
         engine.set_option("dense_group_launch", 0)
         _same(engine.dense_topk(q16, k, filter_dir=filt), got)
         engine.set_option("dense_dir_blocks", 0)
@@ -485,6 +490,7 @@ def test_grouped_launch_sample_pass(engine):
         st, diag = engine.stats(), engine.dense_diag()
         assert st["dense_grouped_launches"] == 1 and st["dense_sample_passes"] == 1 and st["dense_scan_pp3_launches"] == 1, st
         assert diag["uncertified"] == 0 and diag["exhaustive"] == 0 and diag["max_abs_err"] <= diag["margin"], diag
+        assert st["dense_exhaustive_queries"] == 0 and st["dense_group_reruns"] == 0, st
         engine.set_option("dense_group_sample", 0)
         engine.reset_stats()
         _same(engine.dense_topk(q16, k, filter_dir=filt), got)
