@@ -73,8 +73,10 @@ SIGNATURES = {
     "erh_get_kernel_work": (_i32, [_vp, _i32, C.POINTER(_dbl), C.POINTER(_dbl)]),
     "erh_reset_kernel_time": (_i32, [_vp]),
     "erh_set_option": (_i32, [_vp, C.c_char_p, _i64]),
+    "erh_get_option": (_i32, [_vp, C.c_char_p, C.POINTER(_i64)]),
     "erh_dense_check": (_i32, [_vp, _vp]),
     "erh_debug_counters": (_i32, [_vp, _vp]),
+    "erh_debug_live_bytes": (_i64, []),
     "erh_dense_diag": (_i32, [_vp, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_i32)]),
     "erh_dense_exhaustive_count": (_i32, [_vp, C.POINTER(_i32)]),
     "erh_get_stat": (_i32, [_vp, C.c_char_p, C.POINTER(_i64)]),

@@ -4,6 +4,114 @@
 #include "../../include/easyrag_hip.h"
 #include "handle.h"
 
+// ---- options: ONE table of name -> handle field and bounds, walked by erh_set_option and erh_get_option (what the options do:
+// include/easyrag_hip.h).  The few that do more than store a value are named by their field in erh_set_option.
+namespace {
+constexpr int64_t kOptMax = INT64_MAX;
+struct Option {
+    const char *name;
+    int erh_handle::*i32; int64_t erh_handle::*i64;     // the field: one of the two
+    int64_t lo, hi;
+    bool flag;                                          // stores value != 0
+};
+constexpr Option opt_flag(const char *n, int erh_handle::*f) { return {n, f, nullptr, 0, 1, true}; }
+constexpr Option opt_int(const char *n, int erh_handle::*f, int64_t lo, int64_t hi) { return {n, f, nullptr, lo, hi, false}; }
+constexpr Option opt_i64(const char *n, int64_t erh_handle::*f, int64_t lo, int64_t hi) { return {n, nullptr, f, lo, hi, false}; }
+using H = erh_handle;
+const Option kOptions[] = {
+    opt_i64("dense_n0", &H::opt_n0, 1, kOptMax),
+    opt_i64("dense_n1", &H::opt_n1, 0, kOptMax),
+    opt_int("dense_cfg", &H::opt_dense_cfg, 0, 2),
+    opt_flag("dense_readahead", &H::opt_dense_readahead),
+    opt_flag("dense_shuffle", &H::opt_dense_shuffle),                 // takes effect at the next erh_set_dense
+    opt_flag("dense_n1_auto", &H::opt_n1_auto),
+    opt_int("dense_pp", &H::opt_dense_pp, 0, 4),
+    opt_flag("dense_n0_auto", &H::opt_n0_auto),
+    opt_flag("dense_sync", &H::opt_dense_sync),
+    opt_int("dense_selfseed", &H::opt_dense_selfseed, 0, 2),
+    opt_int("n_cus", &H::n_cus, 0, 0),                                // persistent grids: the CUs the caller's stream may use (upper bound: the device's)
+    opt_int("bm25_long_tokens", &H::opt_bm25_long_tokens, 0, 4096),
+    opt_flag("bm25_split_finish", &H::opt_bm25_split_finish),
+    opt_flag("bm25_mixed", &H::opt_bm25_mixed),
+    opt_int("bm25_long_segs", &H::opt_bm25_long_segs, 1, 16),
+    opt_i64("dense_rows_ws_mb", &H::opt_rows_ws_mb, 0, 65536),
+    opt_i64("dense_route_ridge", &H::opt_route_ridge, 1, 4096),
+    opt_flag("dense_group_sample", &H::opt_dense_group_sample),
+    opt_flag("dense_group_launch", &H::opt_dense_group_launch),
+    opt_int("dense_dir_blocks", &H::opt_dense_dir_blocks, 0, 2),
+    opt_i64("dense_dir_block_min_rows", &H::opt_dir_block_min_rows, 1, kOptMax),
+    opt_flag("bm25_dir_range", &H::opt_bm25_dir_range),
+    opt_flag("dense_fin_split", &H::opt_dense_fin_split),
+    opt_flag("dense_tile384", &H::opt_dense_tile384),
+    opt_i64("dense_tile384_max_mb", &H::opt_tile384_max_mb, INT64_MIN, kOptMax),
+    opt_flag("dense_tiled", &H::opt_dense_tiled),                     // building the copy: at the next erh_set_dense
+    opt_flag("dense_speculate", &H::opt_dense_speculate),
+    opt_int("dense_var", &H::opt_dense_var, 0, 3),
+    opt_int("dense_rot", &H::opt_dense_rot, -1, 4096),
+    opt_flag("dense_gemv", &H::opt_dense_gemv),
+    opt_int("dense_gemv_kb", &H::opt_gemv_kb, 16, 32),
+    opt_int("dense_gemv_pipe", &H::opt_gemv_pipe, -1, 1),
+    opt_int("dense_gemv_nt", &H::opt_gemv_nt, -1, 1),
+    opt_int("dense_fin_wgs", &H::opt_fin_wgs, 2, 4),
+    opt_flag("dense_scan_nt", &H::opt_dense_scan_nt),
+    opt_int("dense_gemv_wgs", &H::opt_gemv_wgs, 1, 5),
+    opt_flag("dense_small_single_stage", &H::opt_small_single),
+    opt_flag("dense_persist", &H::opt_dense_persist),
+    opt_int("dense_ablate", &H::opt_dense_ablate, INT32_MIN, INT32_MAX),
+    opt_int("bm25_ablate", &H::opt_bm25_ablate, INT32_MIN, INT32_MAX),
+    opt_flag("debug_counters", &H::opt_debug_counters),
+    opt_int("comm_timeout_s", &H::opt_comm_timeout_s, 1, 86400),
+    opt_flag("bm25_lpt", &H::opt_bm25_lpt),
+    opt_int("bm25_segs", &H::opt_bm25_segs, 0, 64),
+    opt_int("bm25_crossing", &H::opt_bm25_crossing, 0, 2),
+    opt_flag("bm25_ascan", &H::opt_bm25_ascan),
+    opt_flag("bm25_post16", &H::opt_bm25_post16),
+    opt_int("bm25_small", &H::opt_bm25_small, 0, 2),
+    opt_int("hybrid_overlap", &H::opt_hybrid_overlap, -1, 2),
+    opt_flag("bm25_wscan", &H::opt_bm25_wscan),                       // the fine table is built at the next erh_set_bm25_*
+    opt_i64("bm25_fine_max_mb", &H::opt_bm25_fine_max_mb, 0, kOptMax),
+};
+const Option *find_option(const char *name) {
+    for (const Option &o : kOptions) if (!strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+}  // namespace
+
+// What a handle holds besides device buffers.  The buffers are members and free themselves after this body has run, which is why the
+// communicator goes here: it must be gone before gather_send / gather_recv are.
+erh_handle::~erh_handle() {
+    (void)hipSetDevice(device);
+    (void)hipDeviceSynchronize();
+    drain_events(this);
+    for (auto &ev : pool) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
+    if (side) { (void)hipStreamDestroy(side); (void)hipEventDestroy(ev_fork); (void)hipEventDestroy(ev_join); }
+    if (r_flags_host) (void)hipHostFree(r_flags_host);
+    if (comm || comm_pending) (void)erh_comm_destroy(this);
+}
+
+int dense_sets_check(erh_handle *h, hipStream_t st) {
+    erh_handle::DenseSets &S = h->sets;
+    int rc = ERH_OK;
+    h->dense_corrected = false;
+    if (S.n_sub > 0) {
+        rc = dense_check_flags(h, st);
+        if (rc != ERH_OK) return rc;
+        h->diag_maxerr = std::max(h->diag_maxerr, S.acc_maxerr);
+        h->diag_uncert += S.acc_uncert;
+        h->diag_exhaustive += S.acc_exhaustive;
+        S.acc_maxerr = 0; S.acc_uncert = 0; S.acc_exhaustive = 0;
+    } else {
+        h->diag_maxerr = 0; h->diag_uncert = 0; h->diag_exhaustive = 0;
+    }
+    if (h->dense_corrected) {                          // a sub-list changed after the merge: merge all of them again
+        HIPCHK(h, erh::launch_dense_set_merge(h->s_ids.as<int32_t>(), h->s_sc.as<double>(), h->s_len.as<int32_t>(), h->s_tab.as<int32_t>(),
+                                              S.B, S.k, S.d_ids, S.d_sc, S.d_len, st));
+        h->dense_corrected = false;
+    }
+    HIPCHK(h, hipStreamSynchronize(st));
+    return ERH_OK;
+}
+
 extern "C" {
 
 int erh_version(void) { return 200; }
@@ -21,8 +129,6 @@ const char *erh_status_str(int s) {
         default: return "unknown status";
     }
 }
-
-int erh_comm_destroy(erh_handle *h);
 
 int erh_create(int device, erh_handle **out) {
     if (!out) return ERH_ERR_INVALID;
@@ -44,7 +150,7 @@ int erh_create(int device, erh_handle **out) {
         return ERH_ERR_HIP;
     }
     if (h->dstats.ensure(64) != hipSuccess || hipMemset(h->dstats.p, 0, 64) != hipSuccess) {
-        (void)erh_destroy(h);                              // (everything the handle owns so far, whatever that grows to)
+        delete h;
         return ERH_ERR_NOMEM;
     }
     *out = h;
@@ -53,26 +159,6 @@ int erh_create(int device, erh_handle **out) {
 
 int erh_destroy(erh_handle *h) {
     if (!h) return ERH_ERR_INVALID;
-    (void)hipSetDevice(h->device);
-    (void)hipDeviceSynchronize();
-    drain_events(h);
-    for (auto &ev : h->pool) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
-    if (h->side) { (void)hipStreamDestroy(h->side); (void)hipEventDestroy(h->ev_fork); (void)hipEventDestroy(h->ev_join); }
-    DevBuf *bufs[] = {&h->X, &h->Xt, &h->Xt384, &h->Qt, &h->seed_top, &h->scan_sync, &h->content_id, &h->dir_id,
-                      &h->qin, &h->Q16, &h->qnorm, &h->tau, &h->S0, &h->cand, &h->cand_cnt, &h->flags, &h->filt, &h->filt2,
-                      &h->o_ids, &h->o_sc, &h->o_len, &h->qpack, &h->part_sc, &h->part_ids, &h->part_len,
-                      &h->hy_sids, &h->hy_ssc, &h->hy_slen, &h->hy_dids, &h->hy_dsc, &h->hy_dlen,
-                      &h->fa_ids, &h->fa_sc, &h->fa_len, &h->fb_ids, &h->fb_sc, &h->fb_len,
-                      &h->scores_tmp, &h->scores_wide, &h->dbg, &h->dstats, &h->dir_pos, &h->seed_need, &h->bad, &h->ex_ws, &h->bm_redo, &h->fin_ws, &h->dir_rng, &h->Xb, &h->blk_tmp, &h->blk_ids, &h->r_q, &h->r_ids, &h->r_sc, &h->r_len, &h->r_flags, &h->r_tab, &h->r_q16, &h->bm_fin_ids, &h->bm_fin_cnt,
-                      &h->s_tab, &h->s_q, &h->s_ids, &h->s_sc, &h->s_len, &h->lpart_sc, &h->lpart_ids, &h->lpart_len, &h->l_redo,
-                      &h->rw_tab, &h->rw_q, &h->rw_q16, &h->rw_qn, &h->rw_s64, &h->rw_ids, &h->rw_sc, &h->rw_len};
-    for (DevBuf *b : bufs) b->release();
-    if (h->r_flags_host) (void)hipHostFree(h->r_flags_host);
-    for (auto &b : h->bm) b.release();
-    if (h->comm || h->comm_pending) (void)erh_comm_destroy(h);
-    h->gather_send.release();
-    h->gather_recv.release();
-    for (DevBuf *b : {&h->shard_content, &h->sm_a_ids, &h->sm_a_len, &h->sm_b_ids, &h->sm_b_len}) b->release();
     delete h;
     return ERH_OK;
 }
@@ -88,76 +174,40 @@ int erh_sync(erh_handle *h, void *stream) {
 
 int erh_set_option(erh_handle *h, const char *name, int64_t value) {
     if (!h || !name) return ERH_ERR_INVALID;
-    if (!strcmp(name, "dense_n0")) { if (value < 1) return h->fail(ERH_ERR_INVALID, "dense_n0 < 1"); h->opt_n0 = value; return ERH_OK; }
-    if (!strcmp(name, "dense_n1")) { if (value < 0) return h->fail(ERH_ERR_INVALID, "dense_n1 < 0"); h->opt_n1 = value; return ERH_OK; }
-    if (!strcmp(name, "dense_cfg")) { if (value < 0 || value > 2) return h->fail(ERH_ERR_INVALID, "dense_cfg"); h->opt_dense_cfg = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_readahead")) { h->opt_dense_readahead = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_shuffle")) { h->opt_dense_shuffle = value != 0; return ERH_OK; }   // takes effect at the next erh_set_dense
-    if (!strcmp(name, "dense_n1_auto")) { h->opt_n1_auto = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_pp")) { if (value < 0 || value > 4) return h->fail(ERH_ERR_INVALID, "dense_pp"); h->opt_dense_pp = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_n0_auto")) { h->opt_n0_auto = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_sync")) { h->opt_dense_sync = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_selfseed")) { if (value < 0 || value > 2) return h->fail(ERH_ERR_INVALID, "dense_selfseed"); h->opt_dense_selfseed = (int)value; return ERH_OK; }
-    if (!strcmp(name, "n_cus")) {          // persistent grids: the CUs the caller's stream may use (a CU-masked stream); 0 = all of the device
-        if (value < 0 || value > h->n_cus_dev) return h->fail(ERH_ERR_INVALID, "n_cus");
-        h->n_cus = value == 0 ? h->n_cus_dev : (int)value;
-        return ERH_OK;
-    }
-    if (!strcmp(name, "bm25_long_tokens")) { if (value < 0 || value > 4096) return h->fail(ERH_ERR_INVALID, "bm25_long_tokens"); h->opt_bm25_long_tokens = (int)value; return ERH_OK; }
-    if (!strcmp(name, "bm25_split_finish")) { h->opt_bm25_split_finish = value != 0; return ERH_OK; }
-    if (!strcmp(name, "bm25_mixed")) { h->opt_bm25_mixed = value != 0; return ERH_OK; }
-    if (!strcmp(name, "bm25_long_segs")) { if (value < 1 || value > 16) return h->fail(ERH_ERR_INVALID, "bm25_long_segs"); h->opt_bm25_long_segs = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_rows_ws_mb")) { if (value < 0 || value > 65536) return h->fail(ERH_ERR_INVALID, "dense_rows_ws_mb"); h->opt_rows_ws_mb = value; return ERH_OK; }
-    if (!strcmp(name, "dense_route_ridge")) { if (value < 1 || value > 4096) return h->fail(ERH_ERR_INVALID, "dense_route_ridge"); h->opt_route_ridge = value; return ERH_OK; }
-    if (!strcmp(name, "dense_group_sample")) { h->opt_dense_group_sample = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_group_launch")) { h->opt_dense_group_launch = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_dir_blocks")) { if (value < 0 || value > 2) return h->fail(ERH_ERR_INVALID, "dense_dir_blocks"); h->opt_dense_dir_blocks = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_dir_block_min_rows")) { if (value < 1) return h->fail(ERH_ERR_INVALID, "dense_dir_block_min_rows"); h->opt_dir_block_min_rows = value; h->blocks.valid = false; return ERH_OK; }
-    if (!strcmp(name, "bm25_dir_range")) { h->opt_bm25_dir_range = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_fin_split")) { h->opt_dense_fin_split = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_tile384")) { h->opt_dense_tile384 = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_tile384_max_mb")) { h->opt_tile384_max_mb = value; h->xt384_nomem = false; return ERH_OK; }
-    if (!strcmp(name, "dense_tiled")) { h->opt_dense_tiled = value != 0; return ERH_OK; }   // building the copy: at the next erh_set_dense
-    if (!strcmp(name, "dense_speculate")) { h->opt_dense_speculate = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_var")) { if (value < 0 || value > 3) return h->fail(ERH_ERR_INVALID, "dense_var"); h->opt_dense_var = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_rot")) { if (value < -1 || value > 4096) return h->fail(ERH_ERR_INVALID, "dense_rot"); h->opt_dense_rot = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_gemv")) { h->opt_dense_gemv = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_gemv_kb")) { if (value != 16 && value != 32) return h->fail(ERH_ERR_INVALID, "dense_gemv_kb"); h->opt_gemv_kb = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_gemv_pipe")) { if (value < -1 || value > 1) return h->fail(ERH_ERR_INVALID, "dense_gemv_pipe"); h->opt_gemv_pipe = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_gemv_nt")) { if (value < -1 || value > 1) return h->fail(ERH_ERR_INVALID, "dense_gemv_nt"); h->opt_gemv_nt = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_fin_wgs")) { if (value < 2 || value > 4) return h->fail(ERH_ERR_INVALID, "dense_fin_wgs"); erh::dense_finalize_set_wgs((int)value); return ERH_OK; }
-    if (!strcmp(name, "dense_scan_nt")) { h->opt_dense_scan_nt = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_gemv_wgs")) { if (value < 1 || value > 5) return h->fail(ERH_ERR_INVALID, "dense_gemv_wgs"); h->opt_gemv_wgs = (int)value; return ERH_OK; }
-    if (!strcmp(name, "dense_small_single_stage")) { h->opt_small_single = value != 0; return ERH_OK; }
-    if (!strcmp(name, "dense_persist")) { h->opt_dense_persist = value != 0; return ERH_OK; }
-#ifdef ERH_MEASURE
-    if (!strcmp(name, "dense_ablate")) { h->opt_dense_ablate = (int)value; return ERH_OK; }
-    if (!strcmp(name, "bm25_ablate")) { h->opt_bm25_ablate = (int)value; return ERH_OK; }
-#else
-    if (!strcmp(name, "dense_ablate") || !strcmp(name, "bm25_ablate") || !strcmp(name, "debug_counters"))
+    const Option *o = find_option(name);
+    if (!o) return h->fail(ERH_ERR_INVALID, "unknown option");
+    int64_t hi = o->hi;
+    if (o->i32 == &H::n_cus) hi = h->n_cus_dev;
+    if (o->i32 == &H::opt_bm25_small) value = std::min(std::max(value, o->lo), o->hi);          // clamped, not refused
+    if (o->i32 == &H::opt_gemv_kb && value != 16 && value != 32) return h->fail(ERH_ERR_INVALID, o->name);
+#ifndef ERH_MEASURE
+    if (o->i32 == &H::opt_dense_ablate || o->i32 == &H::opt_bm25_ablate || o->i32 == &H::opt_debug_counters)
         return value == 0 ? ERH_OK : h->fail(ERH_ERR_UNSUPPORTED, "measurement option: rebuild the library with ERH_MEASURE=1");
 #endif
-    if (!strcmp(name, "comm_timeout_s")) { if (value < 1 || value > 86400) return h->fail(ERH_ERR_INVALID, "comm_timeout_s"); h->opt_comm_timeout_s = (int)value; return ERH_OK; }
-    if (!strcmp(name, "bm25_lpt")) { h->opt_bm25_lpt = value != 0; return ERH_OK; }
-    if (!strcmp(name, "bm25_segs")) { if (value < 0 || value > 64) return h->fail(ERH_ERR_INVALID, "bm25_segs"); h->opt_bm25_segs = (int)value; return ERH_OK; }
-    if (!strcmp(name, "bm25_crossing")) { if (value < 0 || value > 2) return h->fail(ERH_ERR_INVALID, "bm25_crossing"); h->opt_bm25_crossing = (int)value; return ERH_OK; }
-    if (!strcmp(name, "bm25_ascan")) { h->opt_bm25_ascan = value != 0; return ERH_OK; }
-    if (!strcmp(name, "bm25_post16")) { h->opt_bm25_post16 = value != 0; return ERH_OK; }
-    if (!strcmp(name, "bm25_small")) { h->opt_bm25_small = value < 0 ? 0 : value > 2 ? 2 : (int)value; return ERH_OK; }
-    if (!strcmp(name, "hybrid_overlap")) { if (value < -1 || value > 2) return h->fail(ERH_ERR_INVALID, "hybrid_overlap"); h->opt_hybrid_overlap = (int)value; return ERH_OK; }
-    if (!strcmp(name, "bm25_wscan")) { h->opt_bm25_wscan = value != 0; return ERH_OK; }   // the fine table is built at the next erh_set_bm25_*
-    if (!strcmp(name, "bm25_fine_max_mb")) { if (value < 0) return h->fail(ERH_ERR_INVALID, "bm25_fine_max_mb < 0"); h->opt_bm25_fine_max_mb = value; return ERH_OK; }
-    if (!strcmp(name, "debug_counters")) {
-        h->opt_debug_counters = value != 0;
-        if (value) {
-            HIPCHK(h, hipSetDevice(h->device));
-            HIPCHK(h, h->dbg.ensure(16 * 8));
-            HIPCHK(h, hipMemset(h->dbg.p, 0, 16 * 8));
-        }
-        return ERH_OK;
+    if (o->flag) value = value != 0;
+    if (value < o->lo || value > hi)
+        return h->fail(ERH_ERR_INVALID, o->hi != kOptMax ? o->name : (std::string(o->name) + " < " + std::to_string(o->lo)).c_str());
+    if (o->i64) h->*(o->i64) = value; else h->*(o->i32) = (int)value;
+    if (o->i32 == &H::n_cus && value == 0) h->n_cus = h->n_cus_dev;                              // 0 = all of the device
+    if (o->i64 == &H::opt_dir_block_min_rows) h->blocks.valid = false;
+    if (o->i64 == &H::opt_tile384_max_mb) h->xt384_nomem = false;
+    if (o->i32 == &H::opt_debug_counters && value) {
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, h->dbg.ensure(16 * 8));
+        HIPCHK(h, hipMemset(h->dbg.p, 0, 16 * 8));
     }
-    return h->fail(ERH_ERR_INVALID, "unknown option");
+    return ERH_OK;
 }
+
+int erh_get_option(erh_handle *h, const char *name, int64_t *value) {
+    if (!h || !name || !value) return ERH_ERR_INVALID;
+    const Option *o = find_option(name);
+    if (!o) return h->fail(ERH_ERR_INVALID, "unknown option");
+    *value = o->i64 ? h->*(o->i64) : (int64_t)(h->*(o->i32));
+    return ERH_OK;
+}
+
+int64_t erh_debug_live_bytes(void) { return g_live_dev_bytes.load(std::memory_order_relaxed); }
 
 int erh_set_profiling(erh_handle *h, int enable) {
     if (!h) return ERH_ERR_INVALID;
@@ -336,16 +386,12 @@ int erh_set_dense(erh_handle *h, const void *x, int64_t n, int d, int dtype, int
     HIPCHK(h, hipStreamSynchronize(st));
     // The norm went through the flag words, and the matrix the last dense call scanned is gone: nothing of that call is left for
     // erh_dense_check to read (it would take the norm's bits for a flagged query and the old matrix for the exhaustive path's).
-    h->last = erh_handle::LastDense();
-    h->routed.done = false; h->routed.pending = false;
-    h->sets.on = false;
-    h->qstate = erh_handle::QueryState();
+    h->forget_dense_call();
     h->xnorm_max = xn;
     h->N = n;
     h->d = d;
     h->view_global();
     // tiled copy for the ping-pong scan (dense_scan.hip: dense_tile_rows_kernel); d / 32 >= 8 stages as the kernel wants
-    h->xt384_valid = false;                // (the 384-row copy is rebuilt on first use)
     h->xt_valid = false;
     if (h->opt_dense_tiled && d % 64 == 0 && d >= 256) {
         const int64_t n_tiles = (n + 255) / 256;
@@ -476,7 +522,6 @@ static int bm25_check_payload_sign(erh_handle *h, hipStream_t st) {
                 }
             }
         }
-        p32buf.release();
         if (e != hipSuccess) { S.post.release(); S.post16.release(); return h->fail(e == hipErrorOutOfMemory ? ERH_ERR_NOMEM : ERH_ERR_HIP, "bm25 fixed-point postings", e); }
         S.ascan_ok = ok;
         if (!ok) { S.post.release(); S.post16.release(); }
@@ -541,7 +586,6 @@ int erh_set_bm25_tf(erh_handle *h, int variant, int64_t V, int64_t N, int64_t nn
     hipStream_t st = nullptr;
     HIPCHK(h, h->bm[h->cur].payload.ensure((size_t)(nnz + 1) * es));
     DevBuf d_tf, d_dl, d_idf;
-    auto cleanup = [&]() { d_tf.release(); d_dl.release(); d_idf.release(); };
     hipError_t e = d_tf.ensure((size_t)std::max<int64_t>(nnz, 1) * 4);
     if (e == hipSuccess) e = d_dl.ensure((size_t)N * 4);
     if (e == hipSuccess) e = d_idf.ensure((size_t)V * es);
@@ -552,11 +596,10 @@ int erh_set_bm25_tf(erh_handle *h, int variant, int64_t V, int64_t N, int64_t nn
         e = erh::launch_bm25_payload(variant, V, nnz, h->bm[h->cur].indptr.as<int64_t>(), h->bm[h->cur].doc_ids.as<int32_t>(), d_tf.as<int32_t>(),
                                      d_dl.as<int32_t>(), d_idf.p, avgdl, k1, b, h->bm[h->cur].payload.p, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    cleanup();
     if (e != hipSuccess) { h->bm[h->cur].variant = -1; return h->fail(ERH_ERR_HIP, "erh_set_bm25_tf", e); }
+    d_tf.release(); d_dl.release(); d_idf.release();   // early, to cap peak memory: the fixed-point postings built next do not sit beside them
     return bm25_check_payload_sign(h, st);
 }
-
 
 // ---- index build on the device (first half) --------------------------------------------------
 int erh_build_bm25_index(erh_handle *h, int variant, int64_t V, int64_t N, int64_t n_tokens, const int32_t *token_ids,
@@ -586,69 +629,60 @@ int erh_build_bm25_index(erh_handle *h, int variant, int64_t V, int64_t N, int64
     }
     if (off[N] != T) return h->fail(ERH_ERR_INVALID, "erh_build_bm25_index: document lengths do not sum to the token count");
     DevBuf d_tok, d_off, d_keys, d_sorted, d_uniq, d_cnt, d_first, d_misc, d_temp, d_df, d_dl, d_idf;
-    auto cleanup = [&]() {
-        for (DevBuf *x : {&d_tok, &d_off, &d_keys, &d_sorted, &d_uniq, &d_cnt, &d_first, &d_misc, &d_temp, &d_df, &d_dl, &d_idf})
-            x->release();
-    };
-#define BUILD_CHK(call)                                                                     \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) { cleanup(); return h->fail(e_ == hipErrorOutOfMemory ? ERH_ERR_NOMEM : ERH_ERR_HIP, #call, e_); } \
-    } while (0)
     const size_t Tn = (size_t)std::max<int64_t>(T, 1);
     const int32_t *tok_dev = token_ids;
     if (!is_device_ptr) {
-        BUILD_CHK(d_tok.ensure(Tn * 4));
-        if (T) BUILD_CHK(hipMemcpyAsync(d_tok.p, token_ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(h, d_tok.ensure(Tn * 4));
+        if (T) HIPCHK(h, hipMemcpyAsync(d_tok.p, token_ids, (size_t)T * 4, hipMemcpyHostToDevice, st));
         tok_dev = d_tok.as<int32_t>();
     }
-    BUILD_CHK(d_off.ensure((size_t)(N + 1) * 8));
-    BUILD_CHK(hipMemcpyAsync(d_off.p, off.data(), (size_t)(N + 1) * 8, hipMemcpyHostToDevice, st));
-    BUILD_CHK(d_keys.ensure(Tn * 8));
-    BUILD_CHK(d_sorted.ensure(Tn * 8));
-    BUILD_CHK(d_uniq.ensure(Tn * 8));
-    BUILD_CHK(d_cnt.ensure(Tn * 4));
-    BUILD_CHK(d_first.ensure((size_t)V * 8));
-    BUILD_CHK(d_misc.ensure(64));
-    BUILD_CHK(hipMemsetAsync(d_misc.p, 0, 64, st));
+    HIPCHK(h, d_off.ensure((size_t)(N + 1) * 8));
+    HIPCHK(h, hipMemcpyAsync(d_off.p, off.data(), (size_t)(N + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(h, d_keys.ensure(Tn * 8));
+    HIPCHK(h, d_sorted.ensure(Tn * 8));
+    HIPCHK(h, d_uniq.ensure(Tn * 8));
+    HIPCHK(h, d_cnt.ensure(Tn * 4));
+    HIPCHK(h, d_first.ensure((size_t)V * 8));
+    HIPCHK(h, d_misc.ensure(64));
+    HIPCHK(h, hipMemsetAsync(d_misc.p, 0, 64, st));
     uint32_t *bad_tok = d_misc.as<uint32_t>();
     int32_t *num_runs = d_misc.as<int32_t>() + 4;
-    BUILD_CHK(erh::launch_csr_keys(tok_dev, d_off.as<int64_t>(), T, N, V, d_keys.as<uint64_t>(),
+    HIPCHK(h, erh::launch_csr_keys(tok_dev, d_off.as<int64_t>(), T, N, V, d_keys.as<uint64_t>(),
                                    d_first.as<unsigned long long>(), bad_tok, st));
     int key_bits = 32;
     while (key_bits < 64 && (1ll << (key_bits - 32)) < V) ++key_bits;
     int64_t nnz = 0;
     if (T > 0) {
         size_t tb = 0;
-        BUILD_CHK(erh::csr_sort_rle(d_keys.as<uint64_t>(), d_sorted.as<uint64_t>(), T, key_bits, d_uniq.as<uint64_t>(),
+        HIPCHK(h, erh::csr_sort_rle(d_keys.as<uint64_t>(), d_sorted.as<uint64_t>(), T, key_bits, d_uniq.as<uint64_t>(),
                                     d_cnt.as<int32_t>(), num_runs, nullptr, &tb, st));
-        BUILD_CHK(d_temp.ensure(tb + 256));
+        HIPCHK(h, d_temp.ensure(tb + 256));
         tb = d_temp.cap;
-        BUILD_CHK(erh::csr_sort_rle(d_keys.as<uint64_t>(), d_sorted.as<uint64_t>(), T, key_bits, d_uniq.as<uint64_t>(),
+        HIPCHK(h, erh::csr_sort_rle(d_keys.as<uint64_t>(), d_sorted.as<uint64_t>(), T, key_bits, d_uniq.as<uint64_t>(),
                                     d_cnt.as<int32_t>(), num_runs, d_temp.p, &tb, st));
     }
     uint32_t misc[8] = {0};
-    BUILD_CHK(hipMemcpyAsync(misc, d_misc.p, sizeof misc, hipMemcpyDeviceToHost, st));
-    BUILD_CHK(hipStreamSynchronize(st));
-    if (misc[0]) { cleanup(); return h->fail(ERH_ERR_INVALID, "erh_build_bm25_index: token id out of range"); }
+    HIPCHK(h, hipMemcpyAsync(misc, d_misc.p, sizeof misc, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (misc[0]) return h->fail(ERH_ERR_INVALID, "erh_build_bm25_index: token id out of range");
     nnz = T > 0 ? (int64_t)(int32_t)misc[4] : 0;
     d_keys.release();
     d_sorted.release();
     d_temp.release();
-    BUILD_CHK(S.doc_ids.ensure((size_t)(nnz + 1) * 4));
-    BUILD_CHK(S.tf.ensure((size_t)std::max<int64_t>(nnz, 1) * 4));
-    BUILD_CHK(d_df.ensure((size_t)V * 8));
-    BUILD_CHK(erh::launch_csr_split(d_uniq.as<uint64_t>(), d_cnt.as<int32_t>(), nnz, V, S.doc_ids.as<int32_t>(),
+    HIPCHK(h, S.doc_ids.ensure((size_t)(nnz + 1) * 4));
+    HIPCHK(h, S.tf.ensure((size_t)std::max<int64_t>(nnz, 1) * 4));
+    HIPCHK(h, d_df.ensure((size_t)V * 8));
+    HIPCHK(h, erh::launch_csr_split(d_uniq.as<uint64_t>(), d_cnt.as<int32_t>(), nnz, V, S.doc_ids.as<int32_t>(),
                                     S.tf.as<int32_t>(), d_df.as<unsigned long long>(), st));
     std::vector<unsigned long long> df((size_t)V), first((size_t)V);
-    BUILD_CHK(hipMemcpyAsync(df.data(), d_df.p, (size_t)V * 8, hipMemcpyDeviceToHost, st));
-    BUILD_CHK(hipMemcpyAsync(first.data(), d_first.p, (size_t)V * 8, hipMemcpyDeviceToHost, st));
-    BUILD_CHK(hipStreamSynchronize(st));
+    HIPCHK(h, hipMemcpyAsync(df.data(), d_df.p, (size_t)V * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(first.data(), d_first.p, (size_t)V * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
     // ---- V-sized host work: indptr, idf (+ epsilon floor), avgdl -- the libraries' arithmetic, libm's log --------
     std::vector<int64_t> indptr((size_t)V + 1);
     indptr[0] = 0;
     for (int64_t t = 0; t < V; ++t) indptr[t + 1] = indptr[t] + (int64_t)df[t];
-    if (indptr[V] != nnz) { cleanup(); return h->fail(ERH_ERR_HIP, "erh_build_bm25_index: posting count mismatch"); }
+    if (indptr[V] != nnz) return h->fail(ERH_ERR_HIP, "erh_build_bm25_index: posting count mismatch");
     S.idf_host.assign((size_t)V, 0.0);
     S.average_idf = 0.0;
     const double total_len = (double)off[N];                               // < 2^53: exact
@@ -671,28 +705,26 @@ int erh_build_bm25_index(erh_handle *h, int variant, int64_t V, int64_t N, int64
             if (df[t]) S.idf_host[t] = (double)(float)std::log(1.0 + ((double)(N - (int64_t)df[t]) + 0.5) / ((double)df[t] + 0.5));
     }
     // ---- device: indptr, per-posting payload, skip tables ----------------------------------------------------------
-    BUILD_CHK(S.indptr.ensure((size_t)(V + 1) * 8));
-    BUILD_CHK(hipMemcpyAsync(S.indptr.p, indptr.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(h, S.indptr.ensure((size_t)(V + 1) * 8));
+    HIPCHK(h, hipMemcpyAsync(S.indptr.p, indptr.data(), (size_t)(V + 1) * 8, hipMemcpyHostToDevice, st));
     const size_t es = (variant == ERH_BM25_OKAPI) ? 8 : 4;
-    BUILD_CHK(S.payload.ensure((size_t)(nnz + 1) * es));
-    BUILD_CHK(d_dl.ensure((size_t)N * 4));
-    BUILD_CHK(hipMemcpyAsync(d_dl.p, dl.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
-    BUILD_CHK(d_idf.ensure((size_t)V * es));
+    HIPCHK(h, S.payload.ensure((size_t)(nnz + 1) * es));
+    HIPCHK(h, d_dl.ensure((size_t)N * 4));
+    HIPCHK(h, hipMemcpyAsync(d_dl.p, dl.data(), (size_t)N * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, d_idf.ensure((size_t)V * es));
     std::vector<float> idf32;
     if (variant == ERH_BM25_OKAPI) {
-        BUILD_CHK(hipMemcpyAsync(d_idf.p, S.idf_host.data(), (size_t)V * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d_idf.p, S.idf_host.data(), (size_t)V * 8, hipMemcpyHostToDevice, st));
     } else {
         idf32.resize((size_t)V);
         for (int64_t t = 0; t < V; ++t) idf32[t] = (float)S.idf_host[t];
-        BUILD_CHK(hipMemcpyAsync(d_idf.p, idf32.data(), (size_t)V * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d_idf.p, idf32.data(), (size_t)V * 4, hipMemcpyHostToDevice, st));
     }
-    BUILD_CHK(erh::launch_bm25_payload(variant, V, nnz, S.indptr.as<int64_t>(), S.doc_ids.as<int32_t>(), S.tf.as<int32_t>(),
+    HIPCHK(h, erh::launch_bm25_payload(variant, V, nnz, S.indptr.as<int64_t>(), S.doc_ids.as<int32_t>(), S.tf.as<int32_t>(),
                                        d_dl.as<int32_t>(), d_idf.p, S.avgdl, k1, b, S.payload.p, st));
     int rc = bm25_finish_tables(h, variant, V, N, st);
-    if (rc != ERH_OK) { cleanup(); return rc; }
-    BUILD_CHK(hipStreamSynchronize(st));
-#undef BUILD_CHK
-    cleanup();
+    if (rc != ERH_OK) return rc;
+    HIPCHK(h, hipStreamSynchronize(st));
     S.host_indptr = std::move(indptr);
     S.variant = variant;
     S.V = V;
@@ -700,6 +732,7 @@ int erh_build_bm25_index(erh_handle *h, int variant, int64_t V, int64_t N, int64
     S.nnz = nnz;
     S.built_on_device = true;
     if (out_nnz) *out_nnz = nnz;
+    for (DevBuf *x : {&d_tok, &d_uniq, &d_cnt}) x->release();   // early, to cap peak memory: the fixed-point postings do not sit beside them
     return bm25_check_payload_sign(h, st);
 }
 
@@ -730,9 +763,7 @@ int erh_bm25_release(erh_handle *h, int slot) {
     if (slot < 0 || slot >= ERH_BM25_SLOTS) return h->fail(ERH_ERR_INVALID, "erh_bm25_release: slot out of range");
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());                            // nothing in flight may still read the slot
-    Bm25State &S = h->bm[slot];
-    S.release();
-    S = Bm25State();
+    h->bm[slot] = Bm25State();
     return ERH_OK;
 }
 
@@ -825,12 +856,44 @@ static int stage_query_block(erh_handle *h, const void *q, int q_dtype, int q_is
     return ERH_OK;
 }
 
-static int copy_out(erh_handle *h, int B, int k, const int32_t *d_ids, const double *d_sc, const int32_t *d_len,
-                    int32_t *out_ids, double *out_scores, int32_t *out_len, hipStream_t st) {
-    HIPCHK(h, hipMemcpyAsync(out_ids, d_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out_scores, d_sc, (size_t)B * k * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(out_len, d_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
+// Where a call's kernels write its top-k lists: the caller's rows when they are on the device, else staging buffers of the handle
+// (o_* unless the call names its own) that finish() copies to the caller's host rows.
+struct HostOut {
+    erh_handle *h;
+    int32_t *out_ids; double *out_sc; int32_t *out_len;             // the caller's rows
+    bool host;
+    int B, k;
+    DevBuf *b_ids = &h->o_ids, *b_sc = &h->o_sc, *b_len = &h->o_len;   // the staging buffers (erh_dense_topk_rows points them at its own)
+    int32_t *d_ids; double *d_sc; int32_t *d_len;                   // where the kernels write
+    HostOut(erh_handle *h_, int32_t *ids, double *sc, int32_t *len, int out_is_device, int B_, int k_)
+        : h(h_), out_ids(ids), out_sc(sc), out_len(len), host(!out_is_device), B(B_), k(k_), d_ids(ids), d_sc(sc), d_len(len) {}
+    hipError_t ensure() {                                           // before the first kernel that writes the lists
+        if (!host) return hipSuccess;
+        hipError_t e = b_ids->ensure((size_t)B * k * 4);
+        if (e == hipSuccess) e = b_sc->ensure((size_t)B * k * 8);
+        if (e == hipSuccess) e = b_len->ensure((size_t)B * 4);
+        d_ids = b_ids->as<int32_t>(); d_sc = b_sc->as<double>(); d_len = b_len->as<int32_t>();
+        return e;
+    }
+    int finish(hipStream_t st) {                                    // the call's last step: lists to the host (synchronises), or nothing
+        if (!host) return ERH_OK;
+        HIPCHK(h, hipMemcpyAsync(out_ids, d_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(out_sc, d_sc, (size_t)B * k * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(out_len, d_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        return ERH_OK;
+    }
+};
+
+// The argument checks the three dense entry points share.  mode < 0: the entry point has none, and refuses k < 1 as unsupported
+// (erh_dense_topk_rows).
+static int check_dense_args(erh_handle *h, const char *who, const void *q, bool outs, int B, int k, int q_dtype, int mode) {
+    const std::string w(who);
+    if (!h->X.p || h->N <= 0) return h->fail(ERH_ERR_STATE, (w + " before erh_set_dense").c_str());
+    if (!q || !outs || B <= 0 || (mode >= 0 && k <= 0)) return h->fail(ERH_ERR_INVALID, (w + ": null pointer or non-positive B/k").c_str());
+    if (q_dtype != ERH_F16 && q_dtype != ERH_F32) return h->fail(ERH_ERR_INVALID, (w + ": q_dtype").c_str());
+    if (mode >= 0 && mode != ERH_DENSE_EXACT && mode != ERH_DENSE_FAST) return h->fail(ERH_ERR_INVALID, (w + ": mode").c_str());
+    if (k < 1 || k > 768) return h->fail(ERH_ERR_UNSUPPORTED, (w + (mode >= 0 ? ": k > 768" : ": k outside [1, 768]")).c_str());
     return ERH_OK;
 }
 
@@ -838,36 +901,23 @@ int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, i
                    int B, int k, const int16_t *filter_dir, int mode,
                    int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
     if (!h) return ERH_ERR_INVALID;
-    if (!h->X.p || h->N <= 0) return h->fail(ERH_ERR_STATE, "erh_dense_topk before erh_set_dense");
-    if (!q || !out_ids || !out_scores || !out_len || B <= 0 || k <= 0) return h->fail(ERH_ERR_INVALID, "erh_dense_topk: null pointer or non-positive B/k");
-    if (q_dtype != ERH_F16 && q_dtype != ERH_F32) return h->fail(ERH_ERR_INVALID, "erh_dense_topk: q_dtype");
-    if (mode != ERH_DENSE_EXACT && mode != ERH_DENSE_FAST) return h->fail(ERH_ERR_INVALID, "erh_dense_topk: mode");
-    if (k > 768) return h->fail(ERH_ERR_UNSUPPORTED, "erh_dense_topk: k > 768");
+    int rc = check_dense_args(h, "erh_dense_topk", q, out_ids && out_scores && out_len, B, k, q_dtype, mode);
+    if (rc != ERH_OK) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     const int16_t *filt = nullptr;
-    int rc = stage_filter(h, filter_dir, B, h->N, st, &filt);
+    rc = stage_filter(h, filter_dir, B, h->N, st, &filt);
     if (rc != ERH_OK) return rc;
     const void *qd = nullptr;
     rc = stage_query_block(h, q, q_dtype, q_is_device, B, st, &qd);
     if (rc != ERH_OK) return rc;
-    int32_t *d_ids = out_ids; double *d_sc = out_scores; int32_t *d_len = out_len;
-    if (!out_is_device) {
-        HIPCHK(h, h->o_ids.ensure((size_t)B * k * 4));
-        HIPCHK(h, h->o_sc.ensure((size_t)B * k * 8));
-        HIPCHK(h, h->o_len.ensure((size_t)B * 4));
-        d_ids = h->o_ids.as<int32_t>(); d_sc = h->o_sc.as<double>(); d_len = h->o_len.as<int32_t>();
-    }
+    HostOut out(h, out_ids, out_scores, out_len, out_is_device, B, k);
+    HIPCHK(h, out.ensure());
     h->stats.dense_calls += 1;
     h->sets.on = false;
-    rc = dense_topk_routed(h, qd, q_dtype, normalize_q, B, k, filter_dir, filt, mode, d_ids, d_sc, d_len, st);
-    if (rc != ERH_OK) return rc;
-    if (!out_is_device) {
-        rc = dense_check_flags(h, st);                  // (may run further exhaustive rounds before the copy)
-        if (rc != ERH_OK) return rc;
-        return copy_out(h, B, k, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
-    }
-    return ERH_OK;
+    rc = dense_topk_routed(h, qd, q_dtype, normalize_q, B, k, filter_dir, filt, mode, out.d_ids, out.d_sc, out.d_len, st);
+    if (rc == ERH_OK && out.host) rc = dense_check_flags(h, st);   // (may run further exhaustive rounds before the copy)
+    return rc == ERH_OK ? out.finish(st) : rc;
 }
 
 // Set filters: every (query, allowed class) pair is a sub-query of ONE ordinary class-column batch through dense_topk_routed (in chunks of
@@ -876,43 +926,12 @@ int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, i
 // class, an empty set none.  erh_dense_check -> dense_sets_check: the sub-queries' flag words, and the merge again if they changed a list.
 static constexpr int kSetsChunk = 8192;
 
-}  // extern "C"
-
-int dense_sets_check(erh_handle *h, hipStream_t st) {
-    erh_handle::DenseSets &S = h->sets;
-    int rc = ERH_OK;
-    h->dense_corrected = false;
-    if (S.n_sub > 0) {
-        rc = dense_check_flags(h, st);
-        if (rc != ERH_OK) return rc;
-        h->diag_maxerr = std::max(h->diag_maxerr, S.acc_maxerr);
-        h->diag_uncert += S.acc_uncert;
-        h->diag_exhaustive += S.acc_exhaustive;
-        S.acc_maxerr = 0; S.acc_uncert = 0; S.acc_exhaustive = 0;
-    } else {
-        h->diag_maxerr = 0; h->diag_uncert = 0; h->diag_exhaustive = 0;
-    }
-    if (h->dense_corrected) {                          // a sub-list changed after the merge: merge all of them again
-        HIPCHK(h, erh::launch_dense_set_merge(h->s_ids.as<int32_t>(), h->s_sc.as<double>(), h->s_len.as<int32_t>(), h->s_tab.as<int32_t>(),
-                                              S.B, S.k, S.d_ids, S.d_sc, S.d_len, st));
-        h->dense_corrected = false;
-    }
-    HIPCHK(h, hipStreamSynchronize(st));
-    return ERH_OK;
-}
-
-extern "C" {
-
 int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
                         int B, int k, const int32_t *set_ptr, const int16_t *set_cls, int mode,
                         int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
     if (!h) return ERH_ERR_INVALID;
-    if (!h->X.p || h->N <= 0) return h->fail(ERH_ERR_STATE, "erh_dense_topk_sets before erh_set_dense");
-    if (!q || !out_ids || !out_scores || !out_len || !set_ptr || B <= 0 || k <= 0)
-        return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: null pointer or non-positive B/k");
-    if (q_dtype != ERH_F16 && q_dtype != ERH_F32) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: q_dtype");
-    if (mode != ERH_DENSE_EXACT && mode != ERH_DENSE_FAST) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: mode");
-    if (k > 768) return h->fail(ERH_ERR_UNSUPPORTED, "erh_dense_topk_sets: k > 768");
+    int rc = check_dense_args(h, "erh_dense_topk_sets", q, out_ids && out_scores && out_len && set_ptr, B, k, q_dtype, mode);
+    if (rc != ERH_OK) return rc;
     // the CSR: monotone, classes >= 0 (32767 = matches nothing) and distinct within a set, or the set {-1} alone
     if (set_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: set_ptr[0] != 0");
     for (int b = 0; b < B; ++b)
@@ -965,20 +984,15 @@ int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_devi
     const int32_t *d_ptr = h->s_tab.as<int32_t>();
     const int32_t *d_src = reinterpret_cast<const int32_t *>(h->s_tab.as<char>() + off_src);
     const int16_t *d_cls = reinterpret_cast<const int16_t *>(h->s_tab.as<char>() + off_cls);
-    int32_t *d_ids = out_ids; double *d_sc = out_scores; int32_t *d_len = out_len;
-    if (!out_is_device) {
-        HIPCHK(h, h->o_ids.ensure((size_t)B * k * 4));
-        HIPCHK(h, h->o_sc.ensure((size_t)B * k * 8));
-        HIPCHK(h, h->o_len.ensure((size_t)B * 4));
-        d_ids = h->o_ids.as<int32_t>(); d_sc = h->o_sc.as<double>(); d_len = h->o_len.as<int32_t>();
-    }
+    HostOut out(h, out_ids, out_scores, out_len, out_is_device, B, k);
+    HIPCHK(h, out.ensure());
     h->stats.dense_calls += 1;
     erh_handle::DenseSets &S = h->sets;
     S = erh_handle::DenseSets();
-    S.B = B; S.k = k; S.n_sub = n_sub; S.d_ids = d_ids; S.d_sc = d_sc; S.d_len = d_len;
+    S.B = B; S.k = k; S.n_sub = n_sub; S.d_ids = out.d_ids; S.d_sc = out.d_sc; S.d_len = out.d_len;
     if (n_sub > 0) {
         const void *qd = nullptr;
-        int rc = stage_query_block(h, q, q_dtype, q_is_device, B, st, &qd);
+        rc = stage_query_block(h, q, q_dtype, q_is_device, B, st, &qd);
         if (rc != ERH_OK) return rc;
         const size_t row_bytes = (size_t)h->d * (q_dtype == ERH_F16 ? 2 : 4);
         HIPCHK(h, h->s_q.ensure((size_t)n_sub * row_bytes));
@@ -1003,14 +1017,10 @@ int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_devi
         }
     }
     HIPCHK(h, erh::launch_dense_set_merge(h->s_ids.as<int32_t>(), h->s_sc.as<double>(), h->s_len.as<int32_t>(), d_ptr, B, k,
-                                          d_ids, d_sc, d_len, st));
+                                          out.d_ids, out.d_sc, out.d_len, st));
     S.on = true;
-    if (!out_is_device) {
-        int rc = dense_sets_check(h, st);
-        if (rc != ERH_OK) return rc;
-        return copy_out(h, B, k, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
-    }
-    return ERH_OK;
+    if (out.host) rc = dense_sets_check(h, st);
+    return rc == ERH_OK ? out.finish(st) : rc;
 }
 
 // Explicit row lists (dense_rows.hip).  The call keeps to buffers of its own (rw_*) and touches neither the flag words nor the record of the
@@ -1023,11 +1033,9 @@ int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_devi
                         int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
                         int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
     if (!h) return ERH_ERR_INVALID;
-    if (!h->X.p || h->N <= 0) return h->fail(ERH_ERR_STATE, "erh_dense_topk_rows before erh_set_dense");
-    if (!q || !out_ids || !out_scores || !out_len || !list_of || B <= 0 || n_lists < 0 || (n_lists > 0 && !list_ptr))
-        return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: null pointer, non-positive B or negative n_lists");
-    if (q_dtype != ERH_F16 && q_dtype != ERH_F32) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: q_dtype");
-    if (k < 1 || k > 768) return h->fail(ERH_ERR_UNSUPPORTED, "erh_dense_topk_rows: k outside [1, 768]");
+    const int rc = check_dense_args(h, "erh_dense_topk_rows", q, out_ids && out_scores && out_len && list_of, B, k, q_dtype, -1);
+    if (rc != ERH_OK) return rc;
+    if (n_lists < 0 || (n_lists > 0 && !list_ptr)) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: negative n_lists or null list_ptr");
     const int64_t N = h->N;
     const int d = h->d;
     // the lists: a monotone CSR from 0, every list strictly ascending inside [0, N)
@@ -1093,6 +1101,8 @@ int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_devi
                  o_rows = o_items + items.size() * sizeof(erh::ErhRowsItem), o_of = o_rows + (size_t)total * 4, o_short = o_of + (size_t)B * 4,
                  o_long = o_short + q_short.size() * 4, tab_bytes = o_long + q_long.size() * 4;
     const size_t q_bytes = (size_t)B * d * (q_dtype == ERH_F16 ? 2 : 4);
+    HostOut out(h, out_ids, out_scores, out_len, out_is_device, B, k);
+    out.b_ids = &h->rw_ids; out.b_sc = &h->rw_sc; out.b_len = &h->rw_len;
     {
         hipError_t e = hipSuccess;
         if (need > 0) e = h->rw_s64.ensure((size_t)need * 8);
@@ -1100,11 +1110,7 @@ int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_devi
         if (e == hipSuccess) e = h->rw_q16.ensure((size_t)B * d * 2);
         if (e == hipSuccess) e = h->rw_qn.ensure((size_t)B * 4);
         if (e == hipSuccess && !q_is_device) e = h->rw_q.ensure(q_bytes);
-        if (e == hipSuccess && !out_is_device) {
-            e = h->rw_ids.ensure((size_t)B * k * 4);
-            if (e == hipSuccess) e = h->rw_sc.ensure((size_t)B * k * 8);
-            if (e == hipSuccess) e = h->rw_len.ensure((size_t)B * 4);
-        }
+        if (e == hipSuccess) e = out.ensure();
         if (e != hipSuccess) { (void)hipGetLastError(); return h->fail(ERH_ERR_NOMEM, "erh_dense_topk_rows: work space", e); }
     }
     {
@@ -1126,8 +1132,7 @@ int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_devi
     const erh::ErhRowsItem *d_items = reinterpret_cast<const erh::ErhRowsItem *>(T + o_items);
     const int32_t *d_rows = reinterpret_cast<const int32_t *>(T + o_rows), *d_of = reinterpret_cast<const int32_t *>(T + o_of),
                   *d_short = reinterpret_cast<const int32_t *>(T + o_short), *d_long = reinterpret_cast<const int32_t *>(T + o_long);
-    int32_t *d_ids = out_ids; double *d_sc = out_scores; int32_t *d_len = out_len;
-    if (!out_is_device) { d_ids = h->rw_ids.as<int32_t>(); d_sc = h->rw_sc.as<double>(); d_len = h->rw_len.as<int32_t>(); }
+    int32_t *d_ids = out.d_ids; double *d_sc = out.d_sc; int32_t *d_len = out.d_len;
     const _Float16 *X = h->X.as<_Float16>();
     const _Float16 *Q16 = h->rw_q16.as<_Float16>();
     h->stats.dense_rows_calls += 1;
@@ -1150,8 +1155,7 @@ int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_devi
                                                   d_len, st)); }
         h->stats.dense_rows_long += 1;
     }
-    if (!out_is_device) return copy_out(h, B, k, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
-    return ERH_OK;
+    return out.finish(st);
 }
 
 int erh_bm25_topk(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
@@ -1172,18 +1176,11 @@ int erh_bm25_topk(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, 
     int max_qlen = 0;
     rc = upload_bm25_queries(h, q_indptr, q_tok, B, st, h->bm[h->cur].host_indptr, &bytes, &max_qlen, filt_host, &filt);
     if (rc != ERH_OK) return rc;
-    int32_t *d_ids = out_ids; double *d_sc = out_scores; int32_t *d_len = out_len;
-    if (!out_is_device) {
-        HIPCHK(h, h->o_ids.ensure((size_t)B * k * 4));
-        HIPCHK(h, h->o_sc.ensure((size_t)B * k * 8));
-        HIPCHK(h, h->o_len.ensure((size_t)B * 4));
-        d_ids = h->o_ids.as<int32_t>(); d_sc = h->o_sc.as<double>(); d_len = h->o_len.as<int32_t>();
-    }
+    HostOut out(h, out_ids, out_scores, out_len, out_is_device, B, k);
+    HIPCHK(h, out.ensure());
     h->stats.bm25_calls += 1;
-    rc = bm25_topk_dev(h, h->qptr, h->qtok, B, k, filt, d_ids, d_sc, d_len, bytes, max_qlen, st);
-    if (rc != ERH_OK) return rc;
-    if (!out_is_device) return copy_out(h, B, k, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
-    return ERH_OK;
+    rc = bm25_topk_dev(h, h->qptr, h->qtok, B, k, filt, out.d_ids, out.d_sc, out.d_len, bytes, max_qlen, st);
+    return rc == ERH_OK ? out.finish(st) : rc;
 }
 
 int erh_bm25_scores(erh_handle *h, const int32_t *q_tok, int n_tok, double *out_scores) {
@@ -1223,7 +1220,8 @@ static int fuse_common(erh_handle *h, bool rrf, const int32_t *ids_a, const doub
     const int32_t *cid = h->has_content ? h->content_id.as<int32_t>() : nullptr;
     const int32_t *da = ids_a, *db = ids_b, *dla = len_a, *dlb = len_b;
     const double *dsa = sc_a, *dsb = sc_b;
-    int32_t *d_ids = out_ids; double *d_sc = out_scores; int32_t *d_len = out_len;
+    HostOut out(h, out_ids, out_scores, out_len, io_is_device, B, topk);
+    HIPCHK(h, out.ensure());
     if (!io_is_device) {
         HIPCHK(h, h->fa_ids.ensure((size_t)B * std::max(depth_a, 1) * 4));
         HIPCHK(h, h->fb_ids.ensure((size_t)B * std::max(depth_b, 1) * 4));
@@ -1239,16 +1237,11 @@ static int fuse_common(erh_handle *h, bool rrf, const int32_t *ids_a, const doub
             HIPCHK(h, hipMemcpyAsync(h->fb_sc.p, sc_b, (size_t)B * depth_b * 8, hipMemcpyHostToDevice, st));
             dsa = h->fa_sc.as<double>(); dsb = h->fb_sc.as<double>();
         }
-        HIPCHK(h, h->o_ids.ensure((size_t)B * topk * 4));
-        HIPCHK(h, h->o_sc.ensure((size_t)B * topk * 8));
-        HIPCHK(h, h->o_len.ensure((size_t)B * 4));
-        d_ids = h->o_ids.as<int32_t>(); d_sc = h->o_sc.as<double>(); d_len = h->o_len.as<int32_t>();
     }
     { ProfScope ps(h, st, ERH_K_FUSE, 0, 0);
-      if (rrf) HIPCHK(h, erh::launch_rrf(da, dla, depth_a, db, dlb, depth_b, cid, B, K, topk, d_ids, d_sc, d_len, st));
-      else HIPCHK(h, erh::launch_fusion(da, dsa, dla, depth_a, db, dsb, dlb, depth_b, cid, B, topk, d_ids, d_sc, d_len, st)); }
-    if (!io_is_device) return copy_out(h, B, topk, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
-    return ERH_OK;
+      if (rrf) HIPCHK(h, erh::launch_rrf(da, dla, depth_a, db, dlb, depth_b, cid, B, K, topk, out.d_ids, out.d_sc, out.d_len, st));
+      else HIPCHK(h, erh::launch_fusion(da, dsa, dla, depth_a, db, dsb, dlb, depth_b, cid, B, topk, out.d_ids, out.d_sc, out.d_len, st)); }
+    return out.finish(st);
 }
 
 int erh_rrf(erh_handle *h, const int32_t *ids_a, const int32_t *len_a, int depth_a,
@@ -1433,27 +1426,18 @@ int erh_hybrid_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, 
         if (e_ != hipSuccess && rc == ERH_OK) rc = h->fail(ERH_ERR_HIP, "hipStreamWaitEvent(join)", e_);
     }
     if (rc != ERH_OK) return rc;
-    int32_t *d_ids = out_ids; double *d_sc = out_scores; int32_t *d_len = out_len;
-    if (!out_is_device) {
-        HIPCHK(h, h->o_ids.ensure((size_t)B * topk * 4));
-        HIPCHK(h, h->o_sc.ensure((size_t)B * topk * 8));
-        HIPCHK(h, h->o_len.ensure((size_t)B * 4));
-        d_ids = h->o_ids.as<int32_t>(); d_sc = h->o_sc.as<double>(); d_len = h->o_len.as<int32_t>();
-    }
+    HostOut out(h, out_ids, out_scores, out_len, out_is_device, B, topk);
+    HIPCHK(h, out.ensure());
     const int32_t *cid = h->has_content ? h->content_id.as<int32_t>() : nullptr;
     { ProfScope ps(h, st, ERH_K_FUSE, 0, 0);
       HIPCHK(h, erh::launch_rrf(h->hy_sids.as<int32_t>(), h->hy_slen.as<int32_t>(), k_sparse,
                                 h->hy_dids.as<int32_t>(), h->hy_dlen.as<int32_t>(), k_dense, cid, B, K, topk,
-                                d_ids, d_sc, d_len, st)); }
+                                out.d_ids, out.d_sc, out.d_len, st)); }
     h->last.hybrid = true;
     h->last.k_sparse = k_sparse; h->last.K = K; h->last.topk = topk;
-    h->last.f_ids = d_ids; h->last.f_sc = d_sc; h->last.f_len = d_len;
-    if (!out_is_device) {
-        rc = dense_check_flags(h, st);
-        if (rc != ERH_OK) return rc;
-        return copy_out(h, B, topk, d_ids, d_sc, d_len, out_ids, out_scores, out_len, st);
-    }
-    return ERH_OK;
+    h->last.f_ids = out.d_ids; h->last.f_sc = out.d_sc; h->last.f_len = out.d_len;
+    if (out.host) rc = dense_check_flags(h, st);
+    return rc == ERH_OK ? out.finish(st) : rc;
 }
 
 int erh_debug_dense_scores(erh_handle *h, const void *q_f16_host, int B, int64_t row0, int rows, int use_mfma, float *out) {

@@ -1,5 +1,7 @@
 // Host-side state of libeasyrag_hip.so shared by its translation units (api.hip: the C ABI; pipeline_dense.hip / pipeline_bm25.hip:
 // stage orchestration on the caller's HIP stream; comm.hip: the RCCL exchange): the handle, device buffers, event-based kernel timing.
+// Ownership: a DevBuf frees its allocation when it goes out of scope, and the handle's destructor releases everything else the handle
+// holds (events, side stream, pinned memory, communicator) -- no function keeps a list of what to free.
 // No kernel lives here and no CPU compute path.
 #pragma once
 #include "../../include/easyrag_hip.h"
@@ -21,21 +23,32 @@
 #include <vector>
 #include "kernels.h"
 
+// Bytes held by every live DevBuf of the process (erh_debug_live_bytes): what the lifetime test reads instead of the driver's
+// free-memory figure, which other processes on the card move.
+inline std::atomic<int64_t> g_live_dev_bytes{0};
 
+// One device allocation, owned: freed by release(), by the destructor, and when another buffer is moved in.  Not copyable.
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); }
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); std::swap(p, o.p); std::swap(cap, o.cap); } return *this; }
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        // grow geometrically so that alternating batch sizes do not reallocate every call
-        size_t want = std::max(bytes, cap + cap / 2);
-        hipError_t e = hipMalloc(&p, want);
+        release();                                     // (grows to exactly what is asked for: the largest call so far sets the size)
+        hipError_t e = hipMalloc(&p, bytes);
         if (e != hipSuccess) { p = nullptr; return e; }
-        cap = want;
+        cap = bytes;
+        g_live_dev_bytes.fetch_add((int64_t)cap, std::memory_order_relaxed);
         return hipSuccess;
     }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
+    void release() {
+        if (p) { (void)hipFree(p); g_live_dev_bytes.fetch_sub((int64_t)cap, std::memory_order_relaxed); p = nullptr; cap = 0; }
+    }
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
@@ -60,15 +73,13 @@ struct Bm25State {
     std::vector<int64_t> host_indptr;     // host copy: query validation + algorithmic-byte accounting
     int n_tiles = 0, tile_docs = 0;
     int n_fine = 0;                       // sub-ranges of the fine skip table (0 = not built: block scan only)
-    void release() { indptr.release(); doc_ids.release(); payload.release(); tile_off.release(); fine_off.release(); tf.release(); post.release(); post16.release(); tile_off16.release(); }
 };
-
-
 
 // ncclCommInitRank runs on a helper thread (erh_comm_init); the state outlives a timed-out call
 struct CommInitState { void *comm = nullptr; int rc = -1; std::atomic<int> finished{0}; };
 
 struct erh_handle {
+    ~erh_handle();                           // api.hip: everything a handle holds besides its DevBufs, which free themselves after it
     int device = 0;
     std::string err;
     // dense state
@@ -308,6 +319,7 @@ struct erh_handle {
     DevBuf bad, ex_ws;
     DevBuf fin_ws;                           // dense_finalize_kernel, several workgroups per query (batches of <= 64): sync words + exact scores
     int opt_dense_fin_split = 1;
+    int opt_fin_wgs = 4;                     // workgroups of the final kernel per CU (launch_dense_finalize: 3 / 2 are A/B arms)
     struct LastDense {
         bool valid = false, hybrid = false;
         int B = 0, k = 0;
@@ -318,6 +330,10 @@ struct erh_handle {
         int k_sparse = 0, K = 0, topk = 0;
         int32_t *f_ids = nullptr; double *f_sc = nullptr; int32_t *f_len = nullptr;
     } last;
+    void forget_dense_call() {               // nothing of the last dense call is left for erh_dense_check / erh_debug_dense_query_state to read
+        last = LastDense(); qstate = QueryState();
+        routed.done = routed.pending = sets.on = false;
+    }
 
     int fail(int code, const char *what, hipError_t e = hipSuccess) {
         char buf[512];
@@ -335,8 +351,6 @@ struct erh_handle {
         hipError_t e_ = (call);                                             \
         if (e_ != hipSuccess) return (h)->fail(e_ == hipErrorOutOfMemory ? ERH_ERR_NOMEM : ERH_ERR_HIP, #call, e_); \
     } while (0)
-
-
 
 struct ProfScope {
     erh_handle *h;
@@ -386,7 +400,6 @@ inline void choose_placement(int64_t n, int64_t *mul, int64_t *inv) {
     *inv = g;
     *mul = ((t0 % n) + n) % n;
 }
-
 
 // ---- stage orchestration shared between the translation units (pipeline_dense.hip, pipeline_bm25.hip) -------------------------
 // Dense top-k on device buffers with the dir filter pushed down as a row range where that pays (dense_topk_routed -> dense_topk_dev /

@@ -96,7 +96,6 @@ hipError_t launch_dense_naive(const _Float16 *Q, int B, const _Float16 *X, int64
                               float *out, hipStream_t st);
 
 // ---- dense_gemv.hip: append scan for batches of at most dense_gemv_max_queries() queries ----------------------------
-void dense_finalize_set_wgs(int v);
 int dense_gemv_max_queries();
 hipError_t dense_gemv_init();
 hipError_t launch_dense_gemv_append(const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Q, int B,
@@ -157,6 +156,7 @@ hipError_t launch_dense_finalize(int B, int k, int mode, const float *qnorm, flo
                                  int32_t *out_ids, double *out_scores, int32_t *out_len,
                                  float *diag_maxerr, uint32_t *diag_uncert, uint32_t *bad, int64_t N, int64_t pos_mul,
                                  int64_t pos_inv, const float *tau_verify, int n_cus,
+                                 int fin_wgs /* workgroups of the kernel per CU: 4, or 3 / 2 (option dense_fin_wgs) */,
                                  double *ws_s64 /* null, or dense_finalize_split_max() x kDenseRescoreMax doubles */,
                                  uint32_t *ws_sync /* null, or 2 x dense_finalize_split_max() words, zero between calls */, hipStream_t st,
                                  const ErhGroupIo *gio = nullptr /* grouped call: matrix and placement per query tile, results written to the

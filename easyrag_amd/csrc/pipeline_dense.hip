@@ -266,7 +266,7 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
               HIPCHK(h, erh::launch_dense_finalize(B, k, mode, h->qnorm.as<float>(), h->xnorm_max, d, X, Q16,
                                                    h->cand.as<ErhCand>(), h->cand_cnt.as<uint32_t>(), cap, d_ids, d_sc, d_len,
                                                    reinterpret_cast<float *>(flags + 1), flags + 2, bad, N, pos_mul, pos_inv,
-                                                   h->tau.as<float>(), h->n_cus, fin_s64, fin_sync, st, vo));
+                                                   h->tau.as<float>(), h->n_cus, h->opt_fin_wgs, fin_s64, fin_sync, st, vo));
               HIPCHK(h, erh::launch_dense_exhaustive(bad, B, 0, k, X, N, d, Q16, filter_dev,
                                                      (filter_dev && h->has_dir) ? h->dir_id.as<int16_t>() : nullptr, pos_inv, h->ex_ws.p,
                                                      flags, h->n_cus, d_ids, d_sc, d_len, h->rerun ? nullptr : h->dstats.as<unsigned long long>(), 1 /* count only */, st)); }
@@ -360,7 +360,7 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
       HIPCHK(h, erh::launch_dense_finalize(B, k, mode, h->qnorm.as<float>(), h->xnorm_max, d, X, Q16,
                                            h->cand.as<ErhCand>(), h->cand_cnt.as<uint32_t>(), cap, d_ids, d_sc, d_len,
                                            reinterpret_cast<float *>(flags + 1), flags + 2, bad, N, pos_mul, pos_inv,
-                                           speculate ? h->tau.as<float>() : nullptr, h->n_cus, fin_s64, fin_sync, st, vo));
+                                           speculate ? h->tau.as<float>() : nullptr, h->n_cus, h->opt_fin_wgs, fin_s64, fin_sync, st, vo));
       // queries the candidate budgets could not certify get their exact answer from the exhaustive path: the call enqueues the
       // COUNT only (one workgroup; it settles the "unanswered" word and the flagged count), dense_check_flags -- the synchronisation
       // point every caller passes before it reads results -- runs the exact rounds when, and only when, the count is not zero
@@ -701,7 +701,7 @@ static int dense_topk_grouped(erh_handle *h, const void *q_dev, int q_dtype, int
       HIPCHK(h, erh::launch_dense_finalize(Bpad, k, mode, h->qnorm.as<float>(), h->xnorm_max, d, nullptr, h->Q16.as<_Float16>(),
                                            h->cand.as<ErhCand>(), h->cand_cnt.as<uint32_t>(), cap, d_ids, d_sc, d_len,
                                            reinterpret_cast<float *>(flags + 1), flags + 2, bad, 0, 1, 1, h->tau.as<float>(), h->n_cus,
-                                           nullptr, nullptr, st, &gio));
+                                           h->opt_fin_wgs, nullptr, nullptr, st, &gio));
       HIPCHK(h, erh::launch_dense_exhaustive(bad, Bpad, 0, k, nullptr, P.n_max, d, h->Q16.as<_Float16>(), nullptr, nullptr, 1, h->ex_ws.p,
                                              flags, h->n_cus, d_ids, d_sc, d_len, h->dstats.as<unsigned long long>(), 1 /* count only */, st)); }
     h->stats.dense_grouped_launches += 1;

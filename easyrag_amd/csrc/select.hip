@@ -1017,27 +1017,26 @@ hipError_t launch_cand_refine(int B, int k, const float *qnorm, float xnorm_max,
 // four -0.5 %, eight +2.7 %, sixteen +11 % (profiles/r05m_ab_fin_split.log): the redundant pivot / sort stage of 16 x B workgroups costs more
 // than the shared row gathers save as soon as the queries alone spread over the chip.
 int dense_finalize_split_max() { return 2; }
-// option dense_fin_wgs: workgroups of the final kernel per CU -- 4 (what 64 VGPRs and 36 KiB of LDS allow) or 3 / 2 (A/B arms: unused
-// dynamic LDS per workgroup keeps the others out)
-static int g_fin_wgs = 4;
-void dense_finalize_set_wgs(int v) { g_fin_wgs = v <= 2 ? 2 : v == 3 ? 3 : 4; }
 
 hipError_t launch_dense_finalize(int B, int k, int mode, const float *qnorm, float xnorm_max, int d,
                                  const _Float16 *X, const _Float16 *Q16,
                                  const ErhCand *cand, const uint32_t *cand_cnt, int cap,
                                  int32_t *out_ids, double *out_scores, int32_t *out_len,
                                  float *diag_maxerr, uint32_t *diag_uncert, uint32_t *bad, int64_t N,
-                                 int64_t pos_mul, int64_t pos_inv, const float *tau_verify, int n_cus, double *ws_s64,
+                                 int64_t pos_mul, int64_t pos_inv, const float *tau_verify, int n_cus, int fin_wgs, double *ws_s64,
                                  uint32_t *ws_sync, hipStream_t st, const ErhGroupIo *gio) {
     // workgroups per query: small batches spread a query's row gathers over the chip (EXACT mode only; the work space is optional)
     int G = 1;
     if (mode == 0 && ws_s64 && ws_sync && B <= dense_finalize_split_max() && !(gio && gio->views))
         G = 16;
     (void)n_cus;
+    // fin_wgs (option dense_fin_wgs): workgroups per CU -- 4 (what 64 VGPRs and 36 KiB of LDS allow) or 3 / 2 (A/B arms: unused dynamic
+    // LDS per workgroup keeps the others out)
+    const size_t fin_lds = fin_wgs <= 2 ? 20480 : fin_wgs == 3 ? 4608 : 0;
     ErhGroupIo gv{};
     if (gio) gv = *gio;
 #define ERH_FIN_LAUNCH(QR)                                                                                  \
-    hipLaunchKernelGGL(dense_finalize_kernel<QR>, dim3(B * G), dim3(kFinThreads), g_fin_wgs == 2 ? 20480 : g_fin_wgs == 3 ? 4608 : 0, st, k, mode, qnorm, xnorm_max, d, X, Q16, \
+    hipLaunchKernelGGL(dense_finalize_kernel<QR>, dim3(B * G), dim3(kFinThreads), fin_lds, st, k, mode, qnorm, xnorm_max, d, X, Q16, \
                        cand, cand_cnt, cap, out_ids, out_scores, out_len, diag_maxerr, diag_uncert, bad, N, pos_mul, \
                        pos_inv, tau_verify, G, ws_s64, ws_sync, gv)
     if (d <= 512) ERH_FIN_LAUNCH(1);

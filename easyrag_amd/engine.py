@@ -41,6 +41,11 @@ def queries_to_csr(queries: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.nda
     return indptr, tok
 
 
+def live_device_bytes() -> int:
+    """Device memory the library's buffers hold right now, over all engines of the process (erh_debug_live_bytes)."""
+    return int(_lib.load().erh_debug_live_bytes())
+
+
 class RetrievalEngine:
     """One handle = one GPU's replica of the corpus state (chunk matrix, postings, metadata)."""
 
@@ -588,6 +593,12 @@ class RetrievalEngine:
 
     def set_option(self, name: str, value: int):
         self._check(self._lib.erh_set_option(self._h, name.encode(), int(value)))
+
+    def get_option(self, name: str) -> int:
+        """The value the option holds now (erh_get_option)."""
+        v = C.c_int64()
+        self._check(self._lib.erh_get_option(self._h, name.encode(), C.byref(v)))
+        return int(v.value)
 
     def debug_counters(self):
         out = np.zeros(16, np.uint64)

@@ -77,6 +77,8 @@ int         erh_version(void);
 const char *erh_status_str(int status);
 
 int         erh_create(int device, erh_handle **out);
+/* Synchronises the device, then frees everything the handle owns (device buffers, events, its side stream, pinned memory, the
+ * communicator). */
 int         erh_destroy(erh_handle *h);
 const char *erh_last_error(erh_handle *h);
 int         erh_sync(erh_handle *h, void *stream);
@@ -385,7 +387,7 @@ int erh_reset_kernel_time(erh_handle *h);
  *   dense_scan_nt (0)     256 x 256 ping-pong scan at one query tile per matrix (<= 256 queries, the grouped launch): chunk-side LDS-DMA with
  *                         the non-temporal hint.  Measured +2 % (256 queries), +5.5 % (128), +0.8 % (grouped): off; a parity arm
  *   dense_fin_wgs (4)     workgroups of the final kernel per CU (4: what its 64 VGPRs and 36 KiB of LDS allow; 3 / 2: A/B arms -- select time
- *                         per 1024 queries 0.177 / 0.194 / 0.200 ms at 4 / 3 / 2).  Process-wide.  Same results
+ *                         per 1024 queries 0.177 / 0.194 / 0.200 ms at 4 / 3 / 2).  Per handle.  Same results
  *   dense_gemv_nt (-1)    that stream's chunk loads with the non-temporal hint: -1 on for calls of up to 32 queries unless the sparse
  *                         route of a fused call runs beside it (hybrid_overlap 1), 0 off, 1 on.  Same results
  *   bm25_ascan (1)        fixed-point BM25 scan + exact re-score: the postings are scattered into integer LDS sums in any order
@@ -452,6 +454,9 @@ int erh_reset_kernel_time(erh_handle *h);
  *                         section clocks; results are invalid while an ablate value is non-zero.  The product
  *                         build contains none of these variants and rejects non-zero values (ERH_ERR_UNSUPPORTED). */
 int erh_set_option(erh_handle *h, const char *name, int64_t value);
+/* The value an option holds now: what erh_set_option stored (a flag reads 0 or 1, a clamped value its clamp, n_cus the CU count in
+ * use), or its default.  Unknown name: ERH_ERR_INVALID. */
+int erh_get_option(erh_handle *h, const char *name, int64_t *value);
 
 /* REQUIRED after a dense / hybrid call with DEVICE outputs, before the rows are read or sent anywhere (erh_sync is not
  * a substitute): synchronise `stream` and read the call's flag words (host-output calls do this themselves).  Queries whose candidate
@@ -464,6 +469,10 @@ int erh_dense_check(erh_handle *h, void *stream);
 /* Measurement only: with option "debug_counters" = 1 the scan kernels add per-section shader-clock sums
  * (thread 0 of every workgroup) into 16 counters; this reads and clears them. */
 int erh_debug_counters(erh_handle *h, uint64_t *out16);
+
+/* Debug: bytes of device memory the library's buffers hold right now, over all handles of the process (its own count of what it
+ * allocated and has not freed yet, not the driver's).  0 once every handle is destroyed. */
+int64_t erh_debug_live_bytes(void);
 
 /* Diagnostics of the last dense EXACT call: max |fp64 - fp32| over re-scored candidates, the
  * margin used, and the number of queries whose exactness certificate failed. */
