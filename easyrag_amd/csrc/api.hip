@@ -68,6 +68,7 @@ const Option kOptions[] = {
     opt_flag("bm25_post16", &H::opt_bm25_post16),
     opt_int("bm25_small", &H::opt_bm25_small, 0, 2),
     opt_int("hybrid_overlap", &H::opt_hybrid_overlap, -1, 2),
+    opt_int("hybrid_lazy", &H::opt_hybrid_lazy, 0, 2),
     opt_flag("bm25_wscan", &H::opt_bm25_wscan),                       // the fine table is built at the next erh_set_bm25_*
     opt_i64("bm25_fine_max_mb", &H::opt_bm25_fine_max_mb, 0, kOptMax),
 };
@@ -299,9 +300,23 @@ int erh_get_stat(erh_handle *h, const char *name, int64_t *value) {
         *value = sum;
         return ERH_OK;
     }
-    const int di = !strcmp(name, "dense_exhaustive_queries") ? 0 : !strcmp(name, "bm25_redo_segments") ? 1 : -1;
+    if (!strcmp(name, "dense_rescored_rows_last_call")) {
+        // rows the final kernels of the LAST dense call gathered and re-scored in fp64, summed over its queries (a flagged query: what its
+        // first pass re-scored)
+        HIPCHK(h, hipSetDevice(h->device));
+        HIPCHK(h, hipDeviceSynchronize());
+        const int rows = h->fin_rows.p ? h->fin_rows_n : 0;
+        std::vector<uint32_t> c((size_t)std::max(rows, 0));
+        if (rows > 0) HIPCHK(h, hipMemcpy(c.data(), h->fin_rows.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+        int64_t sum = 0;
+        for (uint32_t v : c) sum += v;
+        *value = sum;
+        return ERH_OK;
+    }
+    const int di = !strcmp(name, "dense_exhaustive_queries") ? 0 : !strcmp(name, "bm25_redo_segments") ? 1 :
+                   !strcmp(name, "hybrid_lazy_queries") ? 2 : -1;
     if (di < 0) return h->fail(ERH_ERR_INVALID, "erh_get_stat: unknown counter");
-    unsigned long long v[2] = {0, 0};
+    unsigned long long v[3] = {0, 0, 0};
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());                       // the counters of everything enqueued so far
     HIPCHK(h, hipMemcpy(v, h->dstats.p, sizeof v, hipMemcpyDeviceToHost));
@@ -785,6 +800,12 @@ int erh_set_doc_meta(erh_handle *h, int64_t N, const int32_t *content_id, const 
             if (content_id[i] < 0) return h->fail(ERH_ERR_INVALID, "erh_set_doc_meta: negative content id");
         HIPCHK(h, h->content_id.ensure((size_t)N * 4));
         HIPCHK(h, hipMemcpy(h->content_id.p, content_id, (size_t)N * 4, hipMemcpyHostToDevice));
+        // M: the largest number of documents behind one RRF key (the lazy final kernel's prefix rule, DESIGN K1)
+        std::vector<int32_t> sorted(content_id, content_id + N);
+        std::sort(sorted.begin(), sorted.end());
+        int64_t best = 1, run = 1;
+        for (int64_t i = 1; i < N; ++i) { run = sorted[i] == sorted[i - 1] ? run + 1 : 1; best = std::max(best, run); }
+        h->content_mult = (int32_t)std::min<int64_t>(best, 2147483647LL);
     }
     h->dir_rng_n = 0;
     h->blocks.valid = false;
@@ -1376,6 +1397,7 @@ int erh_hybrid_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, 
     HIPCHK(h, h->hy_dids.ensure((size_t)B * k_dense * 4));
     HIPCHK(h, h->hy_dsc.ensure((size_t)B * k_dense * 8));
     HIPCHK(h, h->hy_dlen.ensure((size_t)B * 4));
+    HIPCHK(h, h->hy_drank.ensure((size_t)B * k_dense * 4));
     // sparse route (list a), dense route (list b), fusion -- no host round trip.  The two routes do not depend on each
     // other: with hybrid_overlap the sparse route is enqueued on a side stream that forks from the caller's stream (its
     // inputs were staged there) and joins it again in front of the fusion; whatever the dense pipeline leaves idle --
@@ -1411,10 +1433,22 @@ int erh_hybrid_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, 
     }
     h->fork_after_scan = (ov == 2);
     h->sparse_beside = (ov == 1);
+    // hybrid_lazy: the final kernel reads the sparse lists, so they must be complete in front of it -- they are on the caller's stream
+    // (overlap 0); with overlap 1 the join moves from the fusion to the final kernel; overlap 2 starts the sparse route BEHIND the scan
+    // to run it beside the selection kernels, which is the opposite order: that arm keeps the full re-score.
+    // Where it pays (option 1; 2 = wherever it applies): on one stream always; beside the side stream from 4 queries on (measured at 4 / 8 / 16 /
+    // 64 / 256: -1.2 ... -1.7 % wall, profiles/lazy_ab_hybrid_lazy2_b*.log).  One and two queries per call lose (+2.2 % / +2.5 %, one filtered
+    // query +10 %; same logs): those batches split every query over 16 workgroups of the final kernel, which gain nothing from fewer rows
+    // and pay the need set 16 times (select +8 us), and the join in front of the final kernel waits for a sparse route that is no
+    // shorter than the dense scan.  Three queries are unmeasured and keep the full path.
+    const bool lazy = ov != 2 && (h->opt_hybrid_lazy == 2 || (h->opt_hybrid_lazy == 1 && (ov == 0 || B >= 4)));
+    h->lazy.on = lazy; h->lazy.wait_join = (ov == 1);
+    h->lazy.k_sparse = k_sparse; h->lazy.topk = topk; h->lazy.K = K;
     rc = dense_topk_routed(h, qd, q_dtype, normalize_q, B, k_dense, filter_dense, filt_d, ERH_DENSE_EXACT, h->hy_dids.as<int32_t>(),
                            h->hy_dsc.as<double>(), h->hy_dlen.as<int32_t>(), st);
     h->fork_after_scan = false;
     h->sparse_beside = false;
+    h->lazy = erh_handle::HybridLazy();
     if (ov == 2) {                                   // fork behind the dense scan: the sparse route runs beside the selection kernels
         if (rc != ERH_OK) return rc;
         HIPCHK(h, hipStreamWaitEvent(h->side, h->ev_fork, 0));
@@ -1432,8 +1466,9 @@ int erh_hybrid_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, 
     { ProfScope ps(h, st, ERH_K_FUSE, 0, 0);
       HIPCHK(h, erh::launch_rrf(h->hy_sids.as<int32_t>(), h->hy_slen.as<int32_t>(), k_sparse,
                                 h->hy_dids.as<int32_t>(), h->hy_dlen.as<int32_t>(), k_dense, cid, B, K, topk,
-                                out.d_ids, out.d_sc, out.d_len, st)); }
+                                out.d_ids, out.d_sc, out.d_len, st, lazy ? h->hy_drank.as<int32_t>() : nullptr)); }
     h->last.hybrid = true;
+    h->last.d_rank = lazy ? h->hy_drank.as<int32_t>() : nullptr;
     h->last.k_sparse = k_sparse; h->last.K = K; h->last.topk = topk;
     h->last.f_ids = out.d_ids; h->last.f_sc = out.d_sc; h->last.f_len = out.d_len;
     if (out.host) rc = dense_check_flags(h, st);

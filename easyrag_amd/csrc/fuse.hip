@@ -13,6 +13,8 @@
 //   2. the first item of each run is the content's leader (first seen); its score is the sum of the run's
 //      weights in item order (RRF) or its own route score (fusion); the node is the run's last (RRF) / first item;
 //   3. sort the leaders by (score desc, first-seen position asc) = Python's stable sort over dict order; emit topk.
+// RRF with a rank row for list b (erh_hybrid_topk, option hybrid_lazy): list b holds only the items the fused top-k can see, each with
+// its exact rank r in the full list -- weight 1/(r + K), item position la + r - 1, i.e. what the full list would have given it.
 #include "common.h"
 #include "kernels.h"
 
@@ -31,7 +33,8 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(
     const int32_t *__restrict__ ids_a, const double *__restrict__ sc_a, const int32_t *__restrict__ len_a, int depth_a,
     const int32_t *__restrict__ ids_b, const double *__restrict__ sc_b, const int32_t *__restrict__ len_b, int depth_b,
     const int32_t *__restrict__ content_id, int K, int topk, int P,
-    int32_t *__restrict__ out_ids, double *__restrict__ out_scores, int32_t *__restrict__ out_len) {
+    int32_t *__restrict__ out_ids, double *__restrict__ out_scores, int32_t *__restrict__ out_len,
+    const int32_t *__restrict__ rank_b) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int &n_leaders = *reinterpret_cast<int *>(smem);
     uint64_t *key = reinterpret_cast<uint64_t *>(smem + 16);
@@ -48,18 +51,24 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(
     if (la < 0) la = 0;
     if (lb < 0) lb = 0;
     const int n = la + lb;
+    const bool ranked = RRF && rank_b && lb > 0 && rank_b[(int64_t)q * depth_b] != 0;   // (uniform; a row that starts with 0: plain)
     if (tid == 0) n_leaders = 0;
     for (int i = tid; i < P; i += kFuseThreads) {
         uint64_t kv = 0;                                   // empty slots sort to the end
         if (i < n) {
             const bool in_a = i < la;
             const int32_t id = in_a ? ids_a[(int64_t)q * depth_a + i] : ids_b[(int64_t)q * depth_b + (i - la)];
-            doc[i] = id;
+            int rank = in_a ? (i + 1) : (i - la + 1), pos = i;
+            if (ranked && !in_a) {                         // (ranks are distinct and in [1, depth_b]; clamped: a bad row must not write outside the slots)
+                rank = rank_b[(int64_t)q * depth_b + (i - la)];
+                rank = rank < 1 ? 1 : (rank > depth_b ? depth_b : rank);
+                pos = la + rank - 1;
+            }
+            doc[pos] = id;
             const uint32_t c = (uint32_t)(content_id ? content_id[id] : id);
-            kv = ~(((uint64_t)c << 32) | (uint32_t)i);     // descending sort of ~v = ascending (content, position)
+            kv = ~(((uint64_t)c << 32) | (uint32_t)pos);   // descending sort of ~v = ascending (content, position)
             if (RRF) {
-                const int rank = in_a ? (i + 1) : (i - la + 1);
-                w[i] = 1.0 / (double)(rank + K);
+                w[pos] = 1.0 / (double)(rank + K);
             } else {
                 w[i] = in_a ? sc_a[(int64_t)q * depth_a + i] : sc_b[(int64_t)q * depth_b + (i - la)];
             }
@@ -167,13 +176,13 @@ hipError_t fuse_init() {
 hipError_t launch_rrf(const int32_t *ids_a, const int32_t *len_a, int depth_a,
                       const int32_t *ids_b, const int32_t *len_b, int depth_b,
                       const int32_t *content_id, int B, int K, int topk,
-                      int32_t *out_ids, double *out_scores, int32_t *out_len, hipStream_t st) {
+                      int32_t *out_ids, double *out_scores, int32_t *out_len, hipStream_t st, const int32_t *rank_b) {
     if (B <= 0) return hipSuccess;
     int P = 2;
     while (P < depth_a + depth_b) P <<= 1;
     hipLaunchKernelGGL(fuse_kernel<true>, dim3(B), dim3(kFuseThreads), fuse_lds_bytes(P), st,
                        ids_a, (const double *)nullptr, len_a, depth_a, ids_b, (const double *)nullptr, len_b, depth_b,
-                       content_id, K, topk, P, out_ids, out_scores, out_len);
+                       content_id, K, topk, P, out_ids, out_scores, out_len, rank_b);
     return hipGetLastError();
 }
 
@@ -186,7 +195,7 @@ hipError_t launch_fusion(const int32_t *ids_a, const double *sc_a, const int32_t
     while (P < depth_a + depth_b) P <<= 1;
     hipLaunchKernelGGL(fuse_kernel<false>, dim3(B), dim3(kFuseThreads), fuse_lds_bytes(P), st,
                        ids_a, sc_a, len_a, depth_a, ids_b, sc_b, len_b, depth_b,
-                       content_id, 0, topk, P, out_ids, out_scores, out_len);
+                       content_id, 0, topk, P, out_ids, out_scores, out_len, (const int32_t *)nullptr);
     return hipGetLastError();
 }
 

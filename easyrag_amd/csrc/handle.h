@@ -244,13 +244,24 @@ struct erh_handle {
     DevBuf bm_fin_ids, bm_fin_cnt;           // ... its final lists, handed to the batch-wide finish kernel (bm25_split_finish)
     int opt_bm25_split_finish = 0;
     DevBuf hy_sids, hy_ssc, hy_slen, hy_dids, hy_dsc, hy_dlen;
+    // erh_hybrid_topk, option hybrid_lazy (DESIGN K1): the final kernel of the dense route re-scores only the rows the fused top-k can see and
+    // writes (id, exact rank) pairs -- hy_drank is the rank row beside hy_dids (kernels.h: ErhFinLazy).  `lazy` is set around the call's
+    // dense_topk_routed only, like view_out; every dense pipeline of the call (one matrix, routed groups, the grouped launch) reads it.
+    // Re-runs at the check (rerun) and the exhaustive path write plain lists and mark their rows.
+    DevBuf hy_drank;
+    int opt_hybrid_lazy = 1;
+    struct HybridLazy { bool on = false, wait_join = false; int k_sparse = 0, topk = 0, K = 0; } lazy;
+    int32_t content_mult = 1;                // documents that share one content id, at most (erh_set_doc_meta)
+    DevBuf fin_rows;                         // [caller's rows] rows the final kernel re-scored per query (erh_get_stat: dense_rescored_rows_last_call)
+    int fin_rows_n = 0;
     DevBuf fa_ids, fa_sc, fa_len, fb_ids, fb_sc, fb_len;
     DevBuf scores_tmp, scores_wide;
     DevBuf dbg;                              // 16 x u64 section counters (measurement only)
     int opt_debug_counters = 0;
     // erh_get_stat: which kernels answered the calls since erh_create / erh_reset_stats.  Host counters (launch decisions are
     // made on the host) + two device counters the kernels bump themselves, so that device-output pipelines need no round trip:
-    // dstats[0] queries answered by the dense exhaustive path, dstats[1] BM25 (query, segment) pairs handed to the exact scan
+    // dstats[0] queries answered by the dense exhaustive path, dstats[1] BM25 (query, segment) pairs handed to the exact scan,
+    // dstats[2] queries of fused calls whose final kernel re-scored less than the margin set (hybrid_lazy_queries)
     DevBuf dstats;
     struct Stats {
         int64_t dense_calls = 0, dense_scan_pp5 = 0, dense_scan_pp3 = 0, dense_scan_gemv = 0, dense_scan_tile = 0,
@@ -329,6 +340,7 @@ struct erh_handle {
         // hybrid: the fusion to redo after the dense lists changed
         int k_sparse = 0, K = 0, topk = 0;
         int32_t *f_ids = nullptr; double *f_sc = nullptr; int32_t *f_len = nullptr;
+        int32_t *d_rank = nullptr;                                    // ... and the dense lists' rank rows (hybrid_lazy), or null
     } last;
     void forget_dense_call() {               // nothing of the last dense call is left for erh_dense_check / erh_debug_dense_query_state to read
         last = LastDense(); qstate = QueryState();

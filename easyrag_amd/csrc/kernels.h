@@ -45,6 +45,16 @@ struct ErhGroupIo {
     const int32_t *row_map;
     int32_t single_lo;
 };
+// The final kernel's hybrid mode (select.hip: dense_finalize_kernel<.., LAZY>; erh_hybrid_topk with option hybrid_lazy): what it reads of the
+// fused call besides the dense pipeline's own state, and the rank row it writes.  Rows are the CALLER's query rows.
+struct ErhFinLazy {
+    const int32_t *sids, *slen;      // the sparse route's lists [rows][k_sparse] and lengths -- complete before the kernel starts
+    const int32_t *content_id;       // RRF key of a document, or null: the document id
+    int32_t *rank;                   // [rows][k]: exact 1-based dense rank of the row's i-th id; rank[row * k] == 0: a plain list (rank = position)
+    unsigned long long *n_lazy;      // device counter: queries whose need set was smaller than the margin set
+    int32_t k_sparse, topk, K;       // of the fused call
+    int32_t M;                       // documents that share one content id, at most (1 without content ids)
+};
 hipError_t launch_dense_scan_store_grouped(const ErhGroupIo &gio, int n_qt, int n0_max, int n_cus, const _Float16 *Q, int Bpad, int d,
                                            float *S0, int ld_s0, hipStream_t st);
 hipError_t launch_dense_scan_pp_grouped(const ErhGroupIo &gio, int grid, int d, const _Float16 *Q, int Bpad, const float *tau,
@@ -160,13 +170,17 @@ hipError_t launch_dense_finalize(int B, int k, int mode, const float *qnorm, flo
                                  double *ws_s64 /* null, or dense_finalize_split_max() x kDenseRescoreMax doubles */,
                                  uint32_t *ws_sync /* null, or 2 x dense_finalize_split_max() words, zero between calls */, hipStream_t st,
                                  const ErhGroupIo *gio = nullptr /* grouped call: matrix and placement per query tile, results written to the
-                                                                    caller's row q_src[q] with block rows mapped to document ids */);
+                                                                    caller's row q_src[q] with block rows mapped to document ids */,
+                                 uint32_t *rows_out = nullptr /* [caller's rows]: rows each query re-scored */,
+                                 const ErhFinLazy *lazy = nullptr /* EXACT mode of a fused call: re-score only what the fused top-k can see */);
 int dense_finalize_split_max();
 // dense calls routed by dir block: gather the rows idx[0..n) of a query block (row_bytes % 16 == 0), scatter a group's results back
 hipError_t launch_gather_query_rows(const void *q, const int32_t *idx, int n, int row_bytes, void *out, hipStream_t st);
 hipError_t launch_scatter_topk_rows(const int32_t *ids, const double *sc, const int32_t *len, const int32_t *idx, int n, int k,
                                     int32_t id_offset, const int32_t *id_map /* null: id + id_offset; else id_map[id_offset + id] */,
-                                    int32_t *out_ids, double *out_sc, int32_t *out_len, hipStream_t st);
+                                    int32_t *out_ids, double *out_sc, int32_t *out_len, hipStream_t st,
+                                    int32_t *out_rank = nullptr /* a fused call's rank rows: the rows written are marked as plain lists */);
+hipError_t launch_mark_plain_rows(const uint32_t *bad, int B, int k, int32_t *rank, hipStream_t st);   // rank[q * k] = 0 where bad[q] != 0
 // set filters (dense_sets.hip): out row b = the canonical top k of the union of the sub-lists sub_ptr[b] .. sub_ptr[b + 1] of [rows x k]
 // (each canonical, disjoint row sets); k <= 768; no sub-list: length 0
 hipError_t launch_dense_set_merge(const int32_t *sub_ids, const double *sub_sc, const int32_t *sub_len, const int32_t *sub_ptr, int B, int k,
@@ -278,7 +292,9 @@ hipError_t fuse_init();
 hipError_t launch_rrf(const int32_t *ids_a, const int32_t *len_a, int depth_a,
                       const int32_t *ids_b, const int32_t *len_b, int depth_b,
                       const int32_t *content_id, int B, int K, int topk,
-                      int32_t *out_ids, double *out_scores, int32_t *out_len, hipStream_t st);
+                      int32_t *out_ids, double *out_scores, int32_t *out_len, hipStream_t st,
+                      const int32_t *rank_b = nullptr /* [B][depth_b] exact ranks of list b's items (ErhFinLazy::rank: a row that starts with 0
+                                                         is a plain list); null: rank = position */);
 hipError_t launch_fusion(const int32_t *ids_a, const double *sc_a, const int32_t *len_a, int depth_a,
                          const int32_t *ids_b, const double *sc_b, const int32_t *len_b, int depth_b,
                          const int32_t *content_id, int B, int topk,

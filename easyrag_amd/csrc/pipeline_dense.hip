@@ -79,6 +79,22 @@ static hipError_t scan_append(erh_handle *h, const _Float16 *X, int64_t N, int d
                                          h->opt_debug_counters ? h->dbg.as<unsigned long long>() : nullptr, st);
 }
 
+// A fused call's side of the final kernel's hybrid mode (handle.h: HybridLazy)
+static erh::ErhFinLazy dense_lazy_io(erh_handle *h) {
+    erh::ErhFinLazy z{};
+    z.sids = h->hy_sids.as<int32_t>(); z.slen = h->hy_slen.as<int32_t>();
+    z.content_id = h->has_content ? h->content_id.as<int32_t>() : nullptr;
+    z.rank = h->hy_drank.as<int32_t>();
+    z.n_lazy = h->dstats.as<unsigned long long>() + 2;
+    z.k_sparse = h->lazy.k_sparse; z.topk = h->lazy.topk; z.K = h->lazy.K;
+    z.M = h->has_content ? h->content_mult : 1;
+    return z;
+}
+// ... which reads the sparse lists: with the sparse route on the side stream (hybrid_overlap 1) the join moves in front of the kernel
+static hipError_t dense_lazy_join(erh_handle *h, const erh::ErhFinLazy *lz, hipStream_t st) {
+    return (lz && h->lazy.wait_join) ? hipStreamWaitEvent(st, h->ev_join, 0) : hipSuccess;
+}
+
 // ---- dense pipeline on device buffers ------------------------------------------------------------
 int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_q, int B, int k,
                    const int16_t *filter_dev, int mode, int32_t *d_ids, double *d_sc, int32_t *d_len, hipStream_t st) {
@@ -141,6 +157,18 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
         fin_s64 = reinterpret_cast<double *>(h->fin_ws.as<char>() + (size_t)erh::dense_finalize_split_max() * 8);
     }
 
+    // what the final kernel reports / reads beside the pipeline's own state: re-scored rows per query (the caller's rows: a routed call
+    // sized the array), and a fused call's sparse rows (hybrid_lazy) -- not in a re-run at the check, which writes plain lists
+    uint32_t *fin_rows = nullptr;
+    erh::ErhFinLazy lz_io{};
+    const erh::ErhFinLazy *lz = nullptr;
+    if (!h->rerun) {
+        if (!h->view_out.on) { HIPCHK(h, h->fin_rows.ensure((size_t)B * 4)); h->fin_rows_n = B; }
+        fin_rows = h->fin_rows.as<uint32_t>();
+        if (h->lazy.on && mode == ERH_DENSE_EXACT) { lz_io = dense_lazy_io(h); lz = &lz_io; }
+    }
+    // (every path below ends in launch_dense_finalize, which rewrites the first rank word of every row it answers: a fused call's
+    // fusion never sees a rank row of an earlier call)
     erh::ErhGroupIo vo_io{};
     const erh::ErhGroupIo *vo = nullptr;
     if (h->view_out.on) { vo_io.id_map = h->view_out.id_map; vo_io.single_lo = h->view_out.id_lo; vo_io.row_map = h->view_out.row_map; vo = &vo_io; }
@@ -262,11 +290,12 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
               if (e != hipSuccess) rc_scan = h->fail(ERH_ERR_HIP, "dense scan behind the sample pass", e); }
             if (rc_scan != ERH_OK) return rc_scan;
             if (h->fork_after_scan) HIPCHK(h, hipEventRecord(h->ev_fork, st));
+            HIPCHK(h, dense_lazy_join(h, lz, st));
             { ProfScope ps(h, st, ERH_K_DENSE_SELECT, 0, 0);
               HIPCHK(h, erh::launch_dense_finalize(B, k, mode, h->qnorm.as<float>(), h->xnorm_max, d, X, Q16,
                                                    h->cand.as<ErhCand>(), h->cand_cnt.as<uint32_t>(), cap, d_ids, d_sc, d_len,
                                                    reinterpret_cast<float *>(flags + 1), flags + 2, bad, N, pos_mul, pos_inv,
-                                                   h->tau.as<float>(), h->n_cus, h->opt_fin_wgs, fin_s64, fin_sync, st, vo));
+                                                   h->tau.as<float>(), h->n_cus, h->opt_fin_wgs, fin_s64, fin_sync, st, vo, fin_rows, lz));
               HIPCHK(h, erh::launch_dense_exhaustive(bad, B, 0, k, X, N, d, Q16, filter_dev,
                                                      (filter_dev && h->has_dir) ? h->dir_id.as<int16_t>() : nullptr, pos_inv, h->ex_ws.p,
                                                      flags, h->n_cus, d_ids, d_sc, d_len, h->rerun ? nullptr : h->dstats.as<unsigned long long>(), 1 /* count only */, st)); }
@@ -356,11 +385,12 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
         }
     }
     if (h->fork_after_scan) HIPCHK(h, hipEventRecord(h->ev_fork, st));   // the sparse route may start beside the selection kernels
+    HIPCHK(h, dense_lazy_join(h, lz, st));
     { ProfScope ps(h, st, ERH_K_DENSE_SELECT, 0, 0);
       HIPCHK(h, erh::launch_dense_finalize(B, k, mode, h->qnorm.as<float>(), h->xnorm_max, d, X, Q16,
                                            h->cand.as<ErhCand>(), h->cand_cnt.as<uint32_t>(), cap, d_ids, d_sc, d_len,
                                            reinterpret_cast<float *>(flags + 1), flags + 2, bad, N, pos_mul, pos_inv,
-                                           speculate ? h->tau.as<float>() : nullptr, h->n_cus, h->opt_fin_wgs, fin_s64, fin_sync, st, vo));
+                                           speculate ? h->tau.as<float>() : nullptr, h->n_cus, h->opt_fin_wgs, fin_s64, fin_sync, st, vo, fin_rows, lz));
       // queries the candidate budgets could not certify get their exact answer from the exhaustive path: the call enqueues the
       // COUNT only (one workgroup; it settles the "unanswered" word and the flagged count), dense_check_flags -- the synchronisation
       // point every caller passes before it reads results -- runs the exact rounds when, and only when, the count is not zero
@@ -379,7 +409,7 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
 // rounds run here, dense_exhaustive_max() queries at a time (and a fused call's RRF is redone over the corrected dense lists),
 // so the caller always gets an answer.
 static int routed_group_run(erh_handle *h, const erh_handle::RoutedGroup &g, const void *q_rows, int q_dtype, int normalize_q, hipStream_t st, bool direct = false);
-static int routed_group_scatter(erh_handle *h, const erh_handle::RoutedGroup &g, hipStream_t st);
+static int routed_group_scatter(erh_handle *h, const erh_handle::RoutedGroup &g, hipStream_t st, int32_t *d_rank);
 
 int dense_check_flags(erh_handle *h, hipStream_t st) {
     if (h->routed.done) {
@@ -455,7 +485,7 @@ int dense_check_flags(erh_handle *h, hipStream_t st) {
             h->rerun = true;
             int rc = routed_group_run(h, g, q_rows, dt, nq, st);       // (clears routed.done: the check below is the ordinary one)
             if (rc == ERH_OK) rc = dense_check_flags(h, st);
-            if (rc == ERH_OK) rc = routed_group_scatter(h, g, st);
+            if (rc == ERH_OK) rc = routed_group_scatter(h, g, st, saved.hybrid ? saved.d_rank : nullptr);   // (plain lists: the rank rows say so)
             h->rerun = false;
             if (rc != ERH_OK) return rc;
             maxerr = std::max(maxerr, h->diag_maxerr); uncert += h->diag_uncert; exhaustive += h->diag_exhaustive;
@@ -464,7 +494,7 @@ int dense_check_flags(erh_handle *h, hipStream_t st) {
         if (redone && saved.hybrid) {
             const int32_t *cid = h->has_content ? h->content_id.as<int32_t>() : nullptr;
             HIPCHK(h, erh::launch_rrf(h->hy_sids.as<int32_t>(), h->hy_slen.as<int32_t>(), saved.k_sparse, saved.d_ids, saved.d_len,
-                                      saved.k, cid, saved.B, saved.K, saved.topk, saved.f_ids, saved.f_sc, saved.f_len, st));
+                                      saved.k, cid, saved.B, saved.K, saved.topk, saved.f_ids, saved.f_sc, saved.f_len, st, saved.d_rank));
         }
         if (redone) HIPCHK(h, hipStreamSynchronize(st));
         if (redone) h->dense_corrected = true;
@@ -481,6 +511,8 @@ int dense_check_flags(erh_handle *h, hipStream_t st) {
         h->dense_corrected = true;
         const int total = (int)f[3], per = erh::dense_exhaustive_max();
         const erh_handle::LastDense &L = h->last;
+        // a fused call's flagged queries get plain full lists below; the others keep their (id, rank) rows
+        if (L.hybrid && L.d_rank) HIPCHK(h, erh::launch_mark_plain_rows(h->bad.as<uint32_t>(), L.B, L.k, L.d_rank, st));
         for (int skip = 0; skip < total; skip += per)          // (the call enqueued the count only: every answering round runs here)
             HIPCHK(h, erh::launch_dense_exhaustive(h->bad.as<uint32_t>(), L.B, skip, L.k, L.X, L.N, h->d,
                                                    h->Q16.as<_Float16>(), L.filter_dev,
@@ -490,7 +522,7 @@ int dense_check_flags(erh_handle *h, hipStream_t st) {
         if (L.hybrid) {
             const int32_t *cid = h->has_content ? h->content_id.as<int32_t>() : nullptr;
             HIPCHK(h, erh::launch_rrf(h->hy_sids.as<int32_t>(), h->hy_slen.as<int32_t>(), L.k_sparse, L.d_ids, L.d_len,
-                                      L.k, cid, L.B, L.K, L.topk, L.f_ids, L.f_sc, L.f_len, st));
+                                      L.k, cid, L.B, L.K, L.topk, L.f_ids, L.f_sc, L.f_len, st, L.d_rank));
         }
         HIPCHK(h, hipMemcpyAsync(f, h->flags.p, sizeof f, hipMemcpyDeviceToHost, st));
         HIPCHK(h, hipStreamSynchronize(st));
@@ -534,11 +566,11 @@ static int routed_group_run(erh_handle *h, const erh_handle::RoutedGroup &g, con
     return rc;
 }
 
-static int routed_group_scatter(erh_handle *h, const erh_handle::RoutedGroup &g, hipStream_t st) {
+static int routed_group_scatter(erh_handle *h, const erh_handle::RoutedGroup &g, hipStream_t st, int32_t *d_rank) {
     const erh_handle::Routed &R = h->routed;
     HIPCHK(h, erh::launch_scatter_topk_rows(h->r_ids.as<int32_t>(), h->r_sc.as<double>(), h->r_len.as<int32_t>(), h->r_idx + g.at,
                                             g.n, R.k, g.c >= 0 ? (int32_t)h->blocks.lo[g.c] : 0, g.c >= 0 ? h->blk_ids.as<int32_t>() : nullptr,
-                                            R.d_ids, R.d_sc, R.d_len, st));
+                                            R.d_ids, R.d_sc, R.d_len, st, d_rank));
     return ERH_OK;
 }
 
@@ -697,11 +729,15 @@ static int dense_topk_grouped(erh_handle *h, const void *q_dev, int q_dtype, int
         h->stats.dense_scan_pp3 += 1;
     }
     if (h->fork_after_scan) HIPCHK(h, hipEventRecord(h->ev_fork, st));
+    erh::ErhFinLazy lz_io{};
+    const erh::ErhFinLazy *lz = nullptr;
+    if (h->lazy.on && mode == ERH_DENSE_EXACT) { lz_io = dense_lazy_io(h); lz = &lz_io; }
+    HIPCHK(h, dense_lazy_join(h, lz, st));
     { ProfScope ps(h, st, ERH_K_DENSE_SELECT, 0, 0);
       HIPCHK(h, erh::launch_dense_finalize(Bpad, k, mode, h->qnorm.as<float>(), h->xnorm_max, d, nullptr, h->Q16.as<_Float16>(),
                                            h->cand.as<ErhCand>(), h->cand_cnt.as<uint32_t>(), cap, d_ids, d_sc, d_len,
                                            reinterpret_cast<float *>(flags + 1), flags + 2, bad, 0, 1, 1, h->tau.as<float>(), h->n_cus,
-                                           h->opt_fin_wgs, nullptr, nullptr, st, &gio));
+                                           h->opt_fin_wgs, nullptr, nullptr, st, &gio, h->fin_rows.as<uint32_t>(), lz));
       HIPCHK(h, erh::launch_dense_exhaustive(bad, Bpad, 0, k, nullptr, P.n_max, d, h->Q16.as<_Float16>(), nullptr, nullptr, 1, h->ex_ws.p,
                                              flags, h->n_cus, d_ids, d_sc, d_len, h->dstats.as<unsigned long long>(), 1 /* count only */, st)); }
     h->stats.dense_grouped_launches += 1;
@@ -719,6 +755,8 @@ int dense_topk_routed(erh_handle *h, const void *q_dev, int q_dtype, int normali
     const int nc = (int)h->dir_cnt_h.size();
     erh_handle::Routed &R = h->routed;
     R.pending = false;
+    HIPCHK(h, h->fin_rows.ensure((size_t)B * 4));                      // (the final kernels of all the call's pipelines write the caller's rows)
+    h->fin_rows_n = B;
     bool route = h->opt_dense_dir_blocks && filter_host && filter_dev && h->has_dir && nc > 0 && h->Nmeta == h->N && h->opt_dense_ablate == 0;
     std::map<int, std::vector<int32_t>> groups;
     int n_block_groups = 0;

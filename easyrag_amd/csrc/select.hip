@@ -445,7 +445,8 @@ __global__ __launch_bounds__(256) void scatter_topk_rows_kernel(const int32_t *_
                                                                const int32_t *__restrict__ len, const int32_t *__restrict__ idx, int n,
                                                                int k, int32_t id_offset, const int32_t *__restrict__ id_map,
                                                                int32_t *__restrict__ out_ids, double *__restrict__ out_sc,
-                                                               int32_t *__restrict__ out_len) {
+                                                               int32_t *__restrict__ out_len,
+                                                               int32_t *__restrict__ out_rank /* a fused call's rank rows, or null: the rows written here are plain lists */) {
     const int64_t total = (int64_t)n * k;
     for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
         const int r = (int)(o / k), c = (int)(o - (int64_t)r * k);
@@ -453,12 +454,18 @@ __global__ __launch_bounds__(256) void scatter_topk_rows_kernel(const int32_t *_
         const int32_t id = ids[o];
         out_ids[dst] = id < 0 ? id : (id_map ? id_map[id_offset + id] : id + id_offset);   // (a block's rows -> the caller's document ids)
         out_sc[dst] = sc[o];
-        if (c == 0) out_len[idx[r]] = len[r];
+        if (c == 0) { out_len[idx[r]] = len[r]; if (out_rank) out_rank[dst] = 0; }
     }
 }
 
+// a fused call's flagged queries are answered again as plain lists (exhaustive path): their rank rows say so (ErhFinLazy::rank)
+__global__ __launch_bounds__(256) void mark_plain_rows_kernel(const uint32_t *__restrict__ bad, int B, int k, int32_t *__restrict__ rank) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q < B && bad[q] != 0u) rank[(int64_t)q * k] = 0;
+}
+
 // ---- final: select, pinned fp64 re-score of the margin set, rank, emit ------------------------------------------
-// grid = B, block = 1024, static LDS ~ 40 KiB (two workgroups per CU).
+// grid = B (x G for split small batches), block = 512, static LDS 36 KiB (four workgroups per CU at d <= 1024).
 // The candidate list (a few thousand entries, a few hundred of which matter) is never fully sorted: every thread
 // takes the maximum of its strided share, the k-th largest of those 1024 maxima is a lower bound p of the k-th best
 // score, and only entries >= p - margin (about k of them) are gathered into LDS and sorted.
@@ -482,6 +489,30 @@ typedef uint32_t fin_u4 __attribute__((ext_vector_type(4)));
 constexpr int kFinThreads = 512;
 constexpr int kFinSlots = 1024;                      // pivot granularity: strided maxima of 1024 sub-sequences
 
+// Stable compaction of the rows i < m with flag[i] set (ascending) into out[]: the same list in every workgroup of a query.  wcnt: 16 words.
+// Ends with a barrier; the flags must be visible (a barrier behind their last store) when it is called.
+__device__ __forceinline__ int fin_compact(const uint8_t *flag, int m, uint16_t *out, int *wcnt, int tid) {
+    static_assert(erh::kDenseRescoreMax == 2 * kFinThreads, "two rounds of the workgroup cover the re-score set");
+    const int lane = tid & 63, wave = tid >> 6;
+    const bool p0 = tid < m && flag[tid] != 0, p1 = tid + kFinThreads < m && flag[tid + kFinThreads] != 0;
+    const unsigned long long m0 = __ballot(p0), m1 = __ballot(p1);
+    if (lane == 0) { wcnt[wave] = __popcll(m0); wcnt[8 + wave] = __popcll(m1); }
+    __syncthreads();
+    int b0 = 0, b1 = 0, total = 0;
+    for (int x = 0; x < 16; ++x) {
+        const int c = wcnt[x];
+        b0 += (x < wave) ? c : 0;
+        b1 += (x < 8 + wave) ? c : 0;
+        total += c;
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (p0) out[b0 + __popcll(m0 & below)] = (uint16_t)tid;
+    if (p1) out[b1 + __popcll(m1 & below)] = (uint16_t)(tid + kFinThreads);
+    __syncthreads();
+    return total;
+}
+
+
 // QR = rounds of 512 row elements held in registers (d <= 512 * QR runs entirely from them); with QR <= 2 the kernel
 // fits 128 VGPRs, i.e. TWO workgroups per CU (at 144 registers only one fits, and the row gathers of one workgroup do
 // not keep a CU's memory queue busy).  Round 6: with the products from v_fma_mix_f32 (fin_mul_f16: no fp32 copy of the query
@@ -492,7 +523,13 @@ constexpr int kFinSlots = 1024;                      // pivot granularity: strid
 // (profiles/r06zd_ab_fin_wgs4_*.log; option dense_fin_wgs = 2 / 3 keeps the others out with unused dynamic LDS): 0.200 / 0.194 / 0.177 ms
 // at 2 / 3 / 4 workgroups (-11.5 %; 0.198 with the 112-VGPR kernel of the rounds before), the filtered 1024-query step 1.289 -> 1.263;
 // 256 and 512 queries (one / two queries per CU) +-0.
-template <int QR>
+// LAZY (erh_hybrid_topk, option hybrid_lazy; DESIGN K1 "the rows the fused top-k can see"): the fused call reads the dense list's ids and
+// RANKS only, and the fused top t is decided by the exact dense top R_q = M (r* + K) - K (r*: sparse rank of the t-th distinct key, M:
+// documents per content at most) and by the exact ranks of the listed rows whose key the sparse list or that prefix holds.  The kernel
+// re-scores the prefix' margin window and the 2 delta windows of those rows instead of the whole margin set (the same lanes add the same
+// products: every exact score it does compute is the full path's), ranks them by counting, and writes (id, rank) pairs + their number.
+// R_q >= kk, or a sparse list of fewer than t keys: the full path below, and rank[0] = 0 marks the row as a plain list.
+template <int QR, bool LAZY>
 __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize_kernel(
     int k, int mode, const float *__restrict__ qnorm, float xnorm_max, int d,
     const _Float16 *__restrict__ X, const _Float16 *__restrict__ Q16,
@@ -506,7 +543,9 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
     double *__restrict__ ws_s64 /* G > 1: [B][kDenseRescoreMax] exact scores handed to the last workgroup */,
     uint32_t *__restrict__ ws_sync /* G > 1: [B][2] {arrival counter, max error bits}, zero between calls */,
     const erh::ErhGroupIo gio /* views != null: the grouped call (G == 1) -- matrix and placement of the query's tile, results to the
-                                 caller's row, block rows mapped to document ids */) {
+                                 caller's row, block rows mapped to document ids */,
+    uint32_t *__restrict__ rows_out /* [caller's rows] or null: rows this query re-scored (erh_get_stat: dense_rescored_rows_last_call) */,
+    const erh::ErhFinLazy lz /* LAZY only: the query's sparse row, the content ids, the rank row */) {
     __shared__ __attribute__((aligned(16))) uint64_t buf[kFinBuf];
     __shared__ double r_s64[erh::kDenseRescoreMax];
     __shared__ int32_t r_idx[erh::kDenseRescoreMax];
@@ -543,6 +582,10 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
     int32_t *o_ids = out_ids + (int64_t)out_row * k;
     double *o_sc = out_scores + (int64_t)out_row * k;
     if (tid == 0) { if (lead) out_len[out_row] = kk; s_cnt = 0; s_m = 0; s_maxerr = 0; s_lvl = 0; s_last = 1; }
+    if (tid == 0 && lead) {
+        if (rows_out) rows_out[out_row] = 0u;
+        if constexpr (LAZY) lz.rank[(int64_t)out_row * k] = 0;          // a plain list until the lazy path says otherwise
+    }
     if (lead) for (int i = kk + tid; i < k; i += kFinThreads) { o_ids[i] = -1; o_sc[i] = 0.0; }
     if (kk == 0) return;                                                // uniform
 
@@ -629,6 +672,97 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
     const _Float16 *qrow = Q16 + (int64_t)q * d;
     constexpr int RW = (QR == 1) ? 3 : 2;               // rows per wave iteration (as many again are in flight)
     constexpr int kWaves = kFinThreads / 64;
+    // LAZY: the need set.  Its tables live in buf's storage -- the margin set is in r_idx / r_s32 / r_pos now, buf is dead (36 KiB stay 36).
+    int n_need = m;                                     // rows to re-score: nlist[0 .. n_need) (LAZY), else rows 0 .. m
+    [[maybe_unused]] bool lazy = false;
+    [[maybe_unused]] int rq = 0, m_pre = 0;
+    [[maybe_unused]] int32_t *const skey = reinterpret_cast<int32_t *>(buf);        // [1024] keys of the sparse row
+    [[maybe_unused]] int32_t *const rkey = skey + 1024;                             // [1024] keys of the margin set's rows
+    [[maybe_unused]] uint16_t *const nlist = reinterpret_cast<uint16_t *>(rkey + 1024);   // [1024] need list, later the emitted rows
+    [[maybe_unused]] uint8_t *const f_j = reinterpret_cast<uint8_t *>(nlist + 1024);      // [1024] row is in J (its exact rank is wanted)
+    [[maybe_unused]] uint8_t *const f_need = f_j + 1024;                                  // [1024] row is re-scored; later: row is emitted
+    [[maybe_unused]] uint8_t *const f_first = f_need + 1024;                              // [1024] sparse position holds a key's first occurrence
+    [[maybe_unused]] int *const wcnt = reinterpret_cast<int *>(f_first + 1024);           // [16] fin_compact, [16] r*, [17] m_pre
+    static_assert(1024 * (4 + 4 + 2 + 1 + 1 + 1) + 18 * 4 <= kFinBuf * 8 && erh::kDenseRescoreMax <= 1024, "the lazy tables fit buf");
+    [[maybe_unused]] const double two_d = 2.0 * (double)delta;          // (window tests in fp64: exact for fp32 scores)
+    if constexpr (LAZY) {
+        const int32_t *const cid = lz.content_id;
+        const int ks = lz.k_sparse;
+        int ls = lz.slen[out_row];
+        ls = ls < 0 ? 0 : (ls > ks ? ks : ls);
+        for (int i = tid; i < ls; i += kFinThreads) {
+            const int32_t id = lz.sids[(int64_t)out_row * ks + i];
+            skey[i] = cid ? cid[id] : id;
+        }
+        for (int i = tid; i < m; i += kFinThreads) {
+            const int32_t o = r_idx[i];
+            const int32_t doc = id_map ? id_map[id_lo + o] : o;
+            rkey[i] = cid ? cid[doc] : doc;
+            f_j[i] = 0;
+        }
+        if (tid == 0) wcnt[16] = 0;
+        __syncthreads();
+        // r*: sparse rank of the t-th distinct key (R_q >= r*, so positions from kk on cannot give a prefix shorter than the list)
+        if (!cid || lz.M <= 1) {
+            if (tid == 0 && ls >= lz.topk) wcnt[16] = lz.topk;         // documents of a list are distinct, and so are their keys
+        } else {
+            // only positions that can still give R_q < kk: M (r* + K) - K < kk  <=>  r* < (kk + K) / M - K
+            long long lim64 = ((long long)kk + lz.K + lz.M - 1) / lz.M - lz.K;
+            lim64 = lim64 < 0 ? 0 : lim64;
+            const int lim = (int)(lim64 < (long long)ls ? lim64 : (long long)ls);
+            for (int i = tid; i < lim; i += kFinThreads) {
+                const int32_t key = skey[i];
+                bool first = true;
+                for (int j = 0; j < i; ++j) first = first && skey[j] != key;
+                f_first[i] = first ? 1 : 0;
+            }
+            __syncthreads();
+            const int n_first = fin_compact(f_first, lim, nlist, wcnt, tid);   // first occurrences, ascending: the t-th one is r*
+            if (tid == 0 && n_first >= lz.topk) wcnt[16] = (int)nlist[lz.topk - 1] + 1;
+        }
+        __syncthreads();
+        const int rstar = wcnt[16];
+        const long long rq64 = (long long)lz.M * ((long long)rstar + lz.K) - lz.K;
+        lazy = rstar > 0 && rq64 < (long long)kk;                       // uniform
+        if (lazy) {
+            rq = (int)rq64;                                             // 1 <= rq < kk <= m
+            // the prefix' margin window: rows that can be in the exact top rq (the margin-set argument with rq in place of kk)
+            const double thr_p = (double)r_s32[rq - 1] - two_d;
+            for (int i = tid; i < m; i += kFinThreads) {
+                const bool in_i = (double)r_s32[i] >= thr_p;
+                const bool in_n = (i + 1 < m) ? ((double)r_s32[i + 1] >= thr_p) : false;
+                if (in_i && !in_n) wcnt[17] = i + 1;
+            }
+            __syncthreads();
+            m_pre = wcnt[17];
+            // J: rows whose key the sparse list holds, or (content ids) another row of the prefix window -- a superset of the keys of
+            // the exact top rq, which costs re-scored rows, never a result
+            for (int j = wave; j < m; j += kWaves) {
+                const int32_t key = rkey[j];
+                bool found = false;
+                for (int i = lane; i < ls; i += 64) found = found || skey[i] == key;
+                if (cid)
+                    for (int i = lane; i < m_pre; i += 64) found = found || (i != j && rkey[i] == key);
+                if (__any(found) && lane == 0) f_j[j] = 1;
+            }
+            for (int i = tid; i < m; i += kFinThreads) f_need[i] = i < m_pre ? 1 : 0;
+            __syncthreads();
+            for (int j = tid; j < m; j += kFinThreads) {
+                if (!f_j[j]) continue;
+                const double sj = (double)r_s32[j];
+                for (int i = j - 1; i >= m_pre && (double)r_s32[i] <= sj + two_d; --i) f_need[i] = 1;
+                for (int i = j; i < m && (double)r_s32[i] >= sj - two_d; ++i) f_need[i] = 1;
+            }
+            __syncthreads();
+            n_need = fin_compact(f_need, m, nlist, wcnt, tid);
+        } else {
+            for (int i = tid; i < m; i += kFinThreads) nlist[i] = (uint16_t)i;
+            __syncthreads();
+        }
+        if (tid == 0 && lead && lazy && n_need < m) atomicAdd(lz.n_lazy, 1ull);
+    }
+    if (rows_out && tid == 0 && lead) rows_out[out_row] = (uint32_t)n_need;
+#define ERH_FIN_ROW(E) (LAZY ? (int)nlist[E] : (E))
     half8 qreg[QR];
 #pragma unroll
     for (int t = 0; t < QR; ++t) {
@@ -647,8 +781,8 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
 #define ERH_FIN_LOAD(DST, E0)                                                                         \
     do {                                                                                              \
         _Pragma("unroll") for (int r = 0; r < RW; ++r) {                                              \
-            const int e_ = ((E0) + r < m) ? (E0) + r : (E0);                                          \
-            const _Float16 *xr_ = X + (int64_t)r_pos[e_] * d;                                         \
+            const int e_ = ((E0) + r < n_need) ? (E0) + r : (E0);                                     \
+            const _Float16 *xr_ = X + (int64_t)r_pos[ERH_FIN_ROW(e_)] * d;                            \
             _Pragma("unroll") for (int t = 0; t < QR; ++t) {                                          \
                 const int off_ = 512 * t + 8 * lane;                                                  \
                 if (off_ < d) DST[r][t] = *reinterpret_cast<const half8 *>(xr_ + off_);               \
@@ -657,10 +791,10 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
     } while (0)
     const int e_step = G * kWaves * RW;                                 // (G > 1: workgroup `part` takes every G-th group of rows)
     int e0 = (part * kWaves + wave) * RW;
-    if (e0 < m) ERH_FIN_LOAD(xa, e0);
-    for (; e0 < m; e0 += e_step) {
+    if (e0 < n_need) ERH_FIN_LOAD(xa, e0);
+    for (; e0 < n_need; e0 += e_step) {
         const int e1 = e0 + e_step;
-        if (e1 < m) ERH_FIN_LOAD(xb, e1);                               // next pair in flight during the sums below
+        if (e1 < n_need) ERH_FIN_LOAD(xb, e1);                               // next pair in flight during the sums below
         double acc[RW];
 #pragma unroll
         for (int r = 0; r < RW; ++r) acc[r] = 0.0;
@@ -683,8 +817,8 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
         if (d > 512 * QR) {                                             // d > 2048: the tail of the rows straight from memory
 #pragma unroll
             for (int r = 0; r < RW; ++r) {
-                const int e = (e0 + r < m) ? e0 + r : e0;
-                const _Float16 *xr = X + (int64_t)r_pos[e] * d;
+                const int e = (e0 + r < n_need) ? e0 + r : e0;
+                const _Float16 *xr = X + (int64_t)r_pos[ERH_FIN_ROW(e)] * d;
                 for (int off = 512 * QR + 8 * lane; off < d; off += 512) {
                     const half8 qv = *reinterpret_cast<const half8 *>(qrow + off);
                     const half8 xv = *reinterpret_cast<const half8 *>(xr + off);
@@ -700,10 +834,11 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
             float err = 0.f;
 #pragma unroll
             for (int r = 0; r < RW; ++r) {
-                if (e0 + r < m) {
-                    r_s64[e0 + r] = acc[r];
-                    if (G > 1) ws_s64[(int64_t)q * erh::kDenseRescoreMax + e0 + r] = acc[r];
-                    err = fmaxf(err, fabsf((float)(acc[r] - (double)r_s32[e0 + r])));
+                if (e0 + r < n_need) {
+                    const int row = ERH_FIN_ROW(e0 + r);
+                    r_s64[row] = acc[r];
+                    if (G > 1) ws_s64[(int64_t)q * erh::kDenseRescoreMax + row] = acc[r];
+                    err = fmaxf(err, fabsf((float)(acc[r] - (double)r_s32[row])));
                 }
             }
             atomicMax(&s_maxerr, __float_as_uint(err));
@@ -714,6 +849,7 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
             for (int t = 0; t < QR; ++t) xa[r][t] = xb[r][t];
     }
 #undef ERH_FIN_LOAD
+#undef ERH_FIN_ROW
     if (G > 1) {
         // hand-over: scores and error to memory, fence (every writer its own stores), take a ticket; all but the last workgroup of
         // the query are done
@@ -729,12 +865,62 @@ __global__ __launch_bounds__(kFinThreads, (QR <= 2) ? 8 : 2) void dense_finalize
         if (!s_last) return;                                            // uniform
         __threadfence();
         for (int i = tid; i < m; i += kFinThreads)
-            r_s64[i] = __builtin_nontemporal_load(ws_s64 + (int64_t)q * erh::kDenseRescoreMax + i);   // (every row was written by exactly one workgroup)
+            r_s64[i] = __builtin_nontemporal_load(ws_s64 + (int64_t)q * erh::kDenseRescoreMax + i);   // (every re-scored row was written by exactly one workgroup; LAZY: the others are never read)
         if (tid == 0) {
             s_maxerr = atomicExch(&ws_sync[2 * q + 1], 0u);             // ... and the words are zero again for the next call
             ws_sync[2 * q] = 0u;
         }
         __syncthreads();
+    }
+    if constexpr (LAZY) {
+        if (lazy) {                                                     // uniform
+            // exact ranks by counting, in the order of the record sort below: (fp64 desc, index asc)
+            //   a row of J:            1 + #{s_i > s_j + 2 delta} + #{rows of its 2 delta window that beat it}; kept iff <= kk
+            //   another prefix row:    1 + #{rows of the prefix window that beat it};                             kept iff <= rq
+            uint8_t *const f_emit = f_need;
+            __syncthreads();
+            for (int j = tid; j < m; j += kFinThreads) {
+                const bool isj = f_j[j] != 0;
+                int rank = 0;
+                bool emit = false;
+                if (isj || j < m_pre) {
+                    int lo = 0, hi = m_pre;
+                    if (isj) {
+                        const double sj = (double)r_s32[j];
+                        lo = j;
+                        while (lo > 0 && (double)r_s32[lo - 1] <= sj + two_d) --lo;
+                        hi = j + 1;
+                        while (hi < m && (double)r_s32[hi] >= sj - two_d) ++hi;
+                    }
+                    const double ej = r_s64[j];
+                    const int32_t ij = r_idx[j];
+                    int beat = 0;
+                    for (int i = lo; i < hi; ++i) {
+                        const double ei = r_s64[i];
+                        beat += (ei > ej || (ei == ej && r_idx[i] < ij)) ? 1 : 0;
+                    }
+                    rank = 1 + lo + beat;
+                    emit = rank <= (isj ? kk : rq);
+                }
+                f_emit[j] = emit ? 1 : 0;
+                r_pos[j] = rank;                                        // (the stored positions are dead behind the gathers)
+            }
+            __syncthreads();
+            const int n_emit = fin_compact(f_emit, m, nlist, wcnt, tid);
+            int32_t *o_rank = lz.rank + (int64_t)out_row * k;
+            for (int t = tid; t < n_emit; t += kFinThreads) {
+                const int j = nlist[t];
+                o_ids[t] = id_map ? id_map[id_lo + r_idx[j]] : r_idx[j];
+                o_rank[t] = r_pos[j];
+            }
+            if (tid == 0) {
+                out_len[out_row] = n_emit;
+                const float me = __uint_as_float(s_maxerr);
+                atomicMax((unsigned int *)diag_maxerr, __float_as_uint(me));
+                if (uncertified || me > delta) { atomicAdd(diag_uncert, 1u); atomicOr(&bad[q], erh::kDenseBadRescore); }
+            }
+            return;
+        }
     }
     // order by (fp64 desc, index asc): one small record sort (m <= 1024), then the first kk entries are the answer
     const int mp = erh_next_pow2(m < 2 ? 2 : m);
@@ -1024,7 +1210,7 @@ hipError_t launch_dense_finalize(int B, int k, int mode, const float *qnorm, flo
                                  int32_t *out_ids, double *out_scores, int32_t *out_len,
                                  float *diag_maxerr, uint32_t *diag_uncert, uint32_t *bad, int64_t N,
                                  int64_t pos_mul, int64_t pos_inv, const float *tau_verify, int n_cus, int fin_wgs, double *ws_s64,
-                                 uint32_t *ws_sync, hipStream_t st, const ErhGroupIo *gio) {
+                                 uint32_t *ws_sync, hipStream_t st, const ErhGroupIo *gio, uint32_t *rows_out, const ErhFinLazy *lazy) {
     // workgroups per query: small batches spread a query's row gathers over the chip (EXACT mode only; the work space is optional)
     int G = 1;
     if (mode == 0 && ws_s64 && ws_sync && B <= dense_finalize_split_max() && !(gio && gio->views))
@@ -1035,13 +1221,25 @@ hipError_t launch_dense_finalize(int B, int k, int mode, const float *qnorm, flo
     const size_t fin_lds = fin_wgs <= 2 ? 20480 : fin_wgs == 3 ? 4608 : 0;
     ErhGroupIo gv{};
     if (gio) gv = *gio;
-#define ERH_FIN_LAUNCH(QR)                                                                                  \
-    hipLaunchKernelGGL(dense_finalize_kernel<QR>, dim3(B * G), dim3(kFinThreads), fin_lds, st, k, mode, qnorm, xnorm_max, d, X, Q16, \
+    ErhFinLazy lv{};
+    const bool lz = lazy && mode == 0;
+    // (the caller hands the rank rows to the fusion: a launch that cannot write them must fail, not fall back to plain lists without their mark)
+    if (lz && !(lazy->rank && lazy->sids && lazy->slen && lazy->n_lazy && lazy->k_sparse >= 1 && lazy->k_sparse <= 1024 && lazy->M >= 1))
+        return hipErrorInvalidValue;
+    if (lz) lv = *lazy;
+#define ERH_FIN_LAUNCH(QR, LZ)                                                                              \
+    hipLaunchKernelGGL((dense_finalize_kernel<QR, LZ>), dim3(B * G), dim3(kFinThreads), fin_lds, st, k, mode, qnorm, xnorm_max, d, X, Q16, \
                        cand, cand_cnt, cap, out_ids, out_scores, out_len, diag_maxerr, diag_uncert, bad, N, pos_mul, \
-                       pos_inv, tau_verify, G, ws_s64, ws_sync, gv)
-    if (d <= 512) ERH_FIN_LAUNCH(1);
-    else if (d <= 1024) ERH_FIN_LAUNCH(2);
-    else ERH_FIN_LAUNCH(4);
+                       pos_inv, tau_verify, G, ws_s64, ws_sync, gv, rows_out, lv)
+    if (lz) {
+        if (d <= 512) ERH_FIN_LAUNCH(1, true);
+        else if (d <= 1024) ERH_FIN_LAUNCH(2, true);
+        else ERH_FIN_LAUNCH(4, true);
+    } else {
+        if (d <= 512) ERH_FIN_LAUNCH(1, false);
+        else if (d <= 1024) ERH_FIN_LAUNCH(2, false);
+        else ERH_FIN_LAUNCH(4, false);
+    }
 #undef ERH_FIN_LAUNCH
     return hipGetLastError();
 }
@@ -1057,11 +1255,17 @@ hipError_t launch_gather_query_rows(const void *q, const int32_t *idx, int n, in
 
 hipError_t launch_scatter_topk_rows(const int32_t *ids, const double *sc, const int32_t *len, const int32_t *idx, int n, int k,
                                     int32_t id_offset, const int32_t *id_map, int32_t *out_ids, double *out_sc, int32_t *out_len,
-                                    hipStream_t st) {
+                                    hipStream_t st, int32_t *out_rank) {
     if (n <= 0) return hipSuccess;
     const int64_t total = (int64_t)n * k;
     hipLaunchKernelGGL(scatter_topk_rows_kernel, dim3((unsigned)std::min<int64_t>(4096, (total + 255) / 256)), dim3(256), 0, st, ids,
-                       sc, len, idx, n, k, id_offset, id_map, out_ids, out_sc, out_len);
+                       sc, len, idx, n, k, id_offset, id_map, out_ids, out_sc, out_len, out_rank);
+    return hipGetLastError();
+}
+
+hipError_t launch_mark_plain_rows(const uint32_t *bad, int B, int k, int32_t *rank, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(mark_plain_rows_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, bad, B, k, rank);
     return hipGetLastError();
 }
 

@@ -615,7 +615,8 @@ class RetrievalEngine:
     STAT_NAMES = ("dense_calls", "bm25_calls", "hybrid_calls", "dense_scan_pp5_launches", "dense_scan_pp3_launches",
                   "dense_scan_gemv_launches", "dense_scan_tile_launches", "dense_sample_passes", "dense_tile384_nomem",
                   "dense_exhaustive_queries", "bm25_redo_segments", "dense_block_groups", "dense_grouped_launches", "bm25_mixed_launches",
-                  "dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches", "dense_group_reruns")
+                  "dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches", "dense_group_reruns",
+                  "hybrid_lazy_queries", "dense_rescored_rows_last_call")
 
     def stat(self, name: str) -> int:
         """One counter of erh_get_stat (which kernels answered the calls since the last reset_stats)."""

@@ -401,6 +401,16 @@ int erh_reset_kernel_time(erh_handle *h);
  *                         -1 = by batch size: 1 up to 256 queries, where neither scan fills the chip (one query: 0.59 -> 0.54
  *                         ms per call, 64: 0.85 -> 0.77), 0 above (1024 queries: 3.25 / 3.31 against 2.95 ms -- the scans need
  *                         a whole CU's LDS each, so they time-slice instead of sharing)
+ *   hybrid_lazy (1)       erh_hybrid_topk with RRF: the dense route's final kernel re-scores in fp64 only the rows the fused top-k can see --
+ *                         the margin window of the exact dense top R = M (r + K) - K (r: sparse rank of the topk-th distinct key, M: most
+ *                         documents behind one content id) and the 2 delta windows of the listed rows whose key the sparse list or
+ *                         that prefix holds -- and hands (id, exact rank) pairs to the fusion instead of the full ordered list.  The
+ *                         sparse route is complete in front of that kernel: hybrid_overlap 1 joins there instead of before the
+ *                         fusion; hybrid_overlap 2 (sparse route started behind the dense scan) keeps the full re-score.  Queries with
+ *                         R >= k_dense or a sparse list of fewer than topk keys, flagged queries and dense-only calls keep it too.
+ *                         1 = where it was measured to pay: calls on one stream (hybrid_overlap 0: above 256 queries by default) and
+ *                         calls of >= 4 queries beside the side stream (one or two queries per call lose 2 - 10 %: the final kernel
+ *                         splits such queries over 16 workgroups and the join waits for the sparse route); 2 = wherever it applies; 0 = the full re-score everywhere (parity arm).  Same results, bit for bit
  *   bm25_small (2)        shape of the fixed-point scan for batches of >= 8 queries and k <= 384: 2 = 512 threads, 32768-document
  *                         tiles, two documents per accumulator word (16-bit sums, payloads shifted per query); 1 = 512 threads,
  *                         16384-document tiles, 32-bit sums (both: 80 KiB of LDS, two workgroups = two queries per CU);
@@ -499,6 +509,10 @@ int erh_dense_exhaustive_count(erh_handle *h, int32_t *count);
  *                                                      their own because one of their queries was flagged (normally 0)
  *   dense_candidates_last_call                         candidates the last dense pipeline's scan handed to its final kernel, summed over
  *                                                      its queries (read back from the device: synchronises; not reset by erh_reset_stats)
+ *   dense_rescored_rows_last_call                      rows the final kernels of the last dense / fused call gathered and re-scored in fp64, summed
+ *                                                      over its queries (read back from the device: synchronises; not reset by erh_reset_stats)
+ *   hybrid_lazy_queries                                queries of fused calls whose final kernel re-scored less than the margin set (hybrid_lazy;
+ *                                                      device counter, summed over calls)
  *   dense_rows_calls                                   erh_dense_topk_rows calls
  *   dense_rows_short_launches / dense_rows_long_launches  its launches of the short shape (one workgroup per query, lists of at most 2048 rows) /
  *                                                      of the long shape (one score + select pair per chunk of queries)
