@@ -35,6 +35,7 @@ const Option kOptions[] = {
     opt_flag("bm25_mixed", &H::opt_bm25_mixed),
     opt_int("bm25_long_segs", &H::opt_bm25_long_segs, 1, 16),
     opt_i64("dense_rows_ws_mb", &H::opt_rows_ws_mb, 0, 65536),
+    opt_i64("bm25_rows_ws_mb", &H::opt_bm25_rows_ws_mb, 0, 65536),
     opt_i64("dense_route_ridge", &H::opt_route_ridge, 1, 4096),
     opt_flag("dense_group_sample", &H::opt_dense_group_sample),
     opt_flag("dense_group_launch", &H::opt_dense_group_launch),
@@ -146,7 +147,7 @@ int erh_create(int device, erh_handle **out) {
     h->n_cus = h->n_cus_dev = prop.multiProcessorCount;
     if (erh::dense_scan_init() != hipSuccess || erh::select_init() != hipSuccess || erh::bm25_init() != hipSuccess ||
         erh::fuse_init() != hipSuccess || erh::dense_gemv_init() != hipSuccess || erh::shard_merge_init() != hipSuccess ||
-        erh::dense_rows_init() != hipSuccess) {   // (function attributes are per device)
+        erh::dense_rows_init() != hipSuccess || erh::bm25_rows_init() != hipSuccess) {   // (function attributes are per device)
         delete h;
         return ERH_ERR_HIP;
     }
@@ -284,7 +285,8 @@ int erh_get_stat(erh_handle *h, const char *name, int64_t *value) {
         {"bm25_calls", T.bm25_calls}, {"hybrid_calls", T.hybrid_calls}, {"dense_block_groups", T.dense_block_groups},
         {"dense_grouped_launches", T.dense_grouped_launches}, {"bm25_mixed_launches", T.bm25_mixed_launches},
         {"dense_rows_calls", T.dense_rows_calls}, {"dense_rows_short_launches", T.dense_rows_short}, {"dense_rows_long_launches", T.dense_rows_long},
-        {"dense_group_reruns", T.dense_group_reruns}};
+        {"dense_group_reruns", T.dense_group_reruns}, {"bm25_rows_calls", T.bm25_rows_calls},
+        {"bm25_rows_short_launches", T.bm25_rows_short}, {"bm25_rows_long_launches", T.bm25_rows_long}};
     for (const auto &e : host)
         if (!strcmp(name, e.n)) { *value = e.v; return ERH_OK; }
     if (!strcmp(name, "dense_candidates_last_call")) {
@@ -1201,6 +1203,122 @@ int erh_bm25_topk(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, 
     HIPCHK(h, out.ensure());
     h->stats.bm25_calls += 1;
     rc = bm25_topk_dev(h, h->qptr, h->qtok, B, k, filt, out.d_ids, out.d_sc, out.d_len, bytes, max_qlen, st);
+    return rc == ERH_OK ? out.finish(st) : rc;
+}
+
+// Explicit row lists on the sparse route (bm25_rows.hip; launches: pipeline_bm25.hip, bm25_rows_dev).  Everything is checked on the host
+// before anything is enqueued; the call keeps to buffers of its own (bw_*) -- neither the query upload of erh_bm25_topk (qpack) nor the
+// staging rows of any other entry are touched, so a device-output call enqueued in front of it on the stream keeps its results -- and sets
+// no flag words.  Lists of at most kBm25RowsShortMax rows: one launch for all their queries; longer ones: score + select launches per chunk
+// of queries whose score spans fit the work space.
+int erh_bm25_topk_rows(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
+                       int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
+                       int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
+    if (!h) return ERH_ERR_INVALID;
+    const Bm25State &S = h->bm[h->cur];
+    if (S.variant < 0) return h->fail(ERH_ERR_STATE, "erh_bm25_topk_rows before erh_set_bm25_*");
+    if (!q_indptr || !out_ids || !out_scores || !out_len || !list_of || B <= 0) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: null pointer or non-positive B");
+    if (k < 1 || k > 1024) return h->fail(ERH_ERR_UNSUPPORTED, "erh_bm25_topk_rows: k outside [1, 1024]");
+    if (S.nnz >= ((int64_t)1 << 32)) return h->fail(ERH_ERR_UNSUPPORTED, "erh_bm25_topk_rows: more than 2^32 postings");
+    // the queries, as erh_bm25_topk takes them
+    if (q_indptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: q_indptr[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        if (q_indptr[b + 1] < q_indptr[b]) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: q_indptr must be non-decreasing");
+    const int nt = q_indptr[B];
+    if (nt > 0 && !q_tok) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: null q_tok");
+    for (int i = 0; i < nt; ++i)
+        if (q_tok[i] < 0 || q_tok[i] >= S.V) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: query term id out of range");
+    // the lists: a monotone CSR from 0, every list strictly ascending inside [0, N)
+    if (n_lists < 0 || (n_lists > 0 && !list_ptr)) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: negative n_lists or null list_ptr");
+    const int64_t N = S.Nb;
+    int64_t total = 0;
+    if (n_lists > 0) {
+        if (list_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: list_ptr[0] != 0");
+        for (int l = 0; l < n_lists; ++l)
+            if (list_ptr[l + 1] < list_ptr[l]) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: list_ptr decreases");
+        total = list_ptr[n_lists];
+        if (total > 0 && !list_rows) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: null list_rows");
+        for (int l = 0; l < n_lists; ++l)
+            for (int64_t i = list_ptr[l]; i < list_ptr[l + 1]; ++i) {
+                const int32_t r = list_rows[i];
+                if (r < 0 || (int64_t)r >= N) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: row outside [0, N)");
+                if (i > list_ptr[l] && r <= list_rows[i - 1]) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: rows of a list must be strictly ascending");
+            }
+    }
+    for (int b = 0; b < B; ++b)
+        if (list_of[b] < -1 || list_of[b] >= n_lists) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: list_of outside [-1, n_lists)");
+    auto len_of = [&](int b) -> int64_t { const int l = list_of[b]; return l < 0 ? 0 : list_ptr[l + 1] - list_ptr[l]; };
+    auto ntok_of = [&](int b) -> int64_t { return q_indptr[b + 1] - q_indptr[b]; };
+    // shapes by list length; the long queries in chunks whose spans (offsets relative to the chunk) fit the work space, one work item per
+    // (query, segment of kBm25RowsSeg rows)
+    Bm25RowsPlan P;
+    std::vector<int32_t> q_short, q_long;
+    for (int b = 0; b < B; ++b) (len_of(b) <= erh::kBm25RowsShortMax ? q_short : q_long).push_back(b);
+    for (int32_t b : q_short) P.short_searches += len_of(b) * ntok_of(b);
+    const int64_t ws_doubles = std::max<int64_t>((h->opt_bm25_rows_ws_mb << 20) / 8, N);
+    std::vector<int64_t> span_off((size_t)B, 0);
+    std::vector<erh::ErhBm25RowsItem> items;
+    {
+        Bm25RowsPlan::Chunk c{0, 0, 0, 0, 0, 0};
+        for (size_t i = 0; i < q_long.size(); ++i) {
+            const int32_t b = q_long[i];
+            const int64_t len = len_of(b);                                // (len <= N <= ws_doubles: a chunk holds at least one query)
+            if (c.doubles + len > ws_doubles && c.q1 > c.q0) {            // the chunk is full: it ends in front of this query
+                c.item1 = (int64_t)items.size();
+                P.chunks.push_back(c);
+                c = Bm25RowsPlan::Chunk{(int)i, (int)i, (int64_t)items.size(), 0, 0, 0};
+            }
+            span_off[(size_t)b] = c.doubles;
+            c.doubles += len;
+            c.searches += len * ntok_of(b);
+            for (int64_t i0 = 0; i0 < len; i0 += erh::kBm25RowsSeg)
+                items.push_back(erh::ErhBm25RowsItem{b, (int32_t)i0, (int32_t)std::min<int64_t>(erh::kBm25RowsSeg, len - i0)});
+            c.q1 = (int)i + 1;
+        }
+        if (c.q1 > c.q0) { c.item1 = (int64_t)items.size(); P.chunks.push_back(c); }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    // work space first: a call that cannot have it enqueues nothing
+    int64_t need = 0;
+    for (const Bm25RowsPlan::Chunk &c : P.chunks) need = std::max(need, c.doubles);
+    const size_t o_ptr = 0, o_span = o_ptr + ((size_t)n_lists + 1) * 8, o_qptr = o_span + (size_t)B * 8, o_qtok = o_qptr + ((size_t)B + 1) * 4,
+                 o_rows = o_qtok + (size_t)nt * 4, o_of = o_rows + (size_t)total * 4, o_short = o_of + (size_t)B * 4,
+                 o_long = o_short + q_short.size() * 4, o_items = o_long + q_long.size() * 4,
+                 tab_bytes = o_items + items.size() * sizeof(erh::ErhBm25RowsItem);
+    HostOut out(h, out_ids, out_scores, out_len, out_is_device, B, k);
+    out.b_ids = &h->bw_ids; out.b_sc = &h->bw_sc; out.b_len = &h->bw_len;
+    {
+        hipError_t e = hipSuccess;
+        if (need > 0) e = h->bw_s64.ensure((size_t)need * 8);
+        if (e == hipSuccess) e = h->bw_tab.ensure(tab_bytes);
+        if (e == hipSuccess) e = out.ensure();
+        if (e != hipSuccess) { (void)hipGetLastError(); return h->fail(ERH_ERR_NOMEM, "erh_bm25_topk_rows: work space", e); }
+    }
+    {
+        std::vector<char> tab(tab_bytes);
+        const int64_t zero = 0;
+        memcpy(tab.data() + o_ptr, n_lists > 0 ? (const void *)list_ptr : (const void *)&zero, ((size_t)n_lists + 1) * 8);
+        memcpy(tab.data() + o_span, span_off.data(), (size_t)B * 8);
+        memcpy(tab.data() + o_qptr, q_indptr, ((size_t)B + 1) * 4);
+        if (nt > 0) memcpy(tab.data() + o_qtok, q_tok, (size_t)nt * 4);
+        if (total > 0) memcpy(tab.data() + o_rows, list_rows, (size_t)total * 4);
+        memcpy(tab.data() + o_of, list_of, (size_t)B * 4);
+        if (!q_short.empty()) memcpy(tab.data() + o_short, q_short.data(), q_short.size() * 4);
+        if (!q_long.empty()) memcpy(tab.data() + o_long, q_long.data(), q_long.size() * 4);
+        if (!items.empty()) memcpy(tab.data() + o_items, items.data(), items.size() * sizeof(erh::ErhBm25RowsItem));
+        HIPCHK(h, hipMemcpyAsync(h->bw_tab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipStreamSynchronize(st));               // (`tab` is pageable memory of this scope)
+    }
+    const char *T = h->bw_tab.as<char>();
+    P.d_ptr = reinterpret_cast<const int64_t *>(T + o_ptr); P.d_span = reinterpret_cast<const int64_t *>(T + o_span);
+    P.d_qptr = reinterpret_cast<const int32_t *>(T + o_qptr); P.d_qtok = reinterpret_cast<const int32_t *>(T + o_qtok);
+    P.d_rows = reinterpret_cast<const int32_t *>(T + o_rows); P.d_of = reinterpret_cast<const int32_t *>(T + o_of);
+    P.d_short = reinterpret_cast<const int32_t *>(T + o_short); P.d_long = reinterpret_cast<const int32_t *>(T + o_long);
+    P.d_items = reinterpret_cast<const erh::ErhBm25RowsItem *>(T + o_items);
+    P.n_short = (int)q_short.size();
+    h->stats.bm25_rows_calls += 1;
+    const int rc = bm25_rows_dev(h, P, k, out.d_ids, out.d_sc, out.d_len, st);
     return rc == ERH_OK ? out.finish(st) : rc;
 }
 

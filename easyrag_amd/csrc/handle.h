@@ -219,6 +219,12 @@ struct erh_handle {
     // list_of | short-shape queries | long-shape queries; rw_s64: the long shape's score spans (opt_rows_ws_mb, at least one list of N rows)
     DevBuf rw_tab, rw_q, rw_q16, rw_qn, rw_s64, rw_ids, rw_sc, rw_len;
     int64_t opt_rows_ws_mb = 256;
+    // erh_bm25_topk_rows (bm25_rows.hip): again buffers of its own, so that a rows call enqueued behind a device-output erh_bm25_topk /
+    // erh_dense_topk / erh_dense_topk_rows on the same stream leaves that call's query upload, lists and staging alone.  bw_tab: ONE upload
+    // per call -- list_ptr | span offsets | q_indptr | q_tok | rows | list_of | short-shape queries | long-shape queries | work items;
+    // bw_s64: the long shape's score spans (opt_bm25_rows_ws_mb, at least one list of N rows)
+    DevBuf bw_tab, bw_s64, bw_ids, bw_sc, bw_len;
+    int64_t opt_bm25_rows_ws_mb = 256;
     bool dense_corrected = false;            // dense_check_flags changed result rows (exhaustive rounds or a group run again)
     DevBuf dir_rng;                          // {first document, last + 1} of every dir class (erh_set_doc_meta): a filtered BM25 query walks those tiles only
     int dir_rng_n = 0;
@@ -267,7 +273,7 @@ struct erh_handle {
         int64_t dense_calls = 0, dense_scan_pp5 = 0, dense_scan_pp3 = 0, dense_scan_gemv = 0, dense_scan_tile = 0,
                 dense_sample_passes = 0, dense_tile384_nomem = 0, bm25_calls = 0, hybrid_calls = 0, dense_block_groups = 0,
                 dense_grouped_launches = 0, bm25_mixed_launches = 0, dense_rows_calls = 0, dense_rows_short = 0, dense_rows_long = 0,
-                dense_group_reruns = 0;
+                dense_group_reruns = 0, bm25_rows_calls = 0, bm25_rows_short = 0, bm25_rows_long = 0;
     } stats;
     // multi-GPU exchange (erh_comm_* / erh_allgather_topk): RCCL communicator + packed send / receive rows
     void *comm = nullptr;
@@ -426,6 +432,17 @@ int dense_sets_check(erh_handle *h, hipStream_t st);   // erh_dense_check after 
 int bm25_topk_dev(erh_handle *h, const int32_t *qptr_dev, const int32_t *qtok_dev, int B, int k,
                   const int16_t *filter_dev, int32_t *d_ids, double *d_sc, int32_t *d_len, double postings_bytes,
                   int max_qlen, hipStream_t st);
+// erh_bm25_topk_rows behind its validation and upload: the short-shape launch and the long shape's score + select pairs, chunk after chunk
+struct Bm25RowsPlan {
+    const int32_t *d_qptr, *d_qtok, *d_rows, *d_of, *d_short, *d_long;
+    const int64_t *d_ptr, *d_span;
+    const erh::ErhBm25RowsItem *d_items;
+    int n_short = 0;
+    int64_t short_searches = 0;              // (row, token) pairs of the short shape
+    struct Chunk { int q0, q1; int64_t item0, item1, doubles, searches; };
+    std::vector<Chunk> chunks;               // of the long-shape queries d_long[q0 .. q1): their spans fit bw_s64 together
+};
+int bm25_rows_dev(erh_handle *h, const Bm25RowsPlan &plan, int k, int32_t *d_ids, double *d_sc, int32_t *d_len, hipStream_t st);
 int upload_bm25_queries(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, hipStream_t st,
                         const std::vector<int64_t> &host_indptr, double *bytes, int *max_qlen,
                         const int16_t *filt_a = nullptr, const int16_t **filt_a_dev = nullptr /* validated host filter column(s) that ride along */,

@@ -341,4 +341,34 @@ hipError_t launch_dense_rows_select(const double *S64, const int64_t *span_off, 
                                     const int32_t *list_of, const int32_t *qord, int n_q, int k, int32_t *out_ids, double *out_sc,
                                     int32_t *out_len, hipStream_t st);
 
+// ---- bm25_rows.hip: exact BM25 top k over explicit per-query row lists (erh_bm25_topk_rows) ---------------------------------------------
+constexpr int kBm25RowsShortMax = 2048;    // lists up to this length: one launch, one workgroup per query (sums sorted in LDS)
+constexpr int kBm25RowsSeg = 2048;         // long shape: rows of a list per work item of the score kernel
+// The index of the selected slot as the kernels read it.  tile_off: n_tab + 1 entries per term at 2^tab_shift documents, or null (every
+// search then takes the term's whole posting range).  Posting positions are 32-bit: nnz < 2^32.
+struct ErhBm25RowsIndex {
+    const int64_t *indptr;
+    const int32_t *doc_ids;
+    const void *payload;                   // fp64 (f64 != 0: ERH_BM25_OKAPI) or fp32 (ERH_BM25_BM25S): the type the sums run in
+    const int32_t *tile_off;
+    int32_t n_tab, tab_shift, f64;
+};
+// One work item of the long shape's score kernel: rows i0 .. i0 + n_rows of query q's list -> S64[span_off[q] + i0 ..)
+struct ErhBm25RowsItem {
+    int32_t q, i0, n_rows;
+};
+static_assert(sizeof(ErhBm25RowsItem) == 12, "ErhBm25RowsItem layout");
+hipError_t bm25_rows_init();
+// q_indptr / q_tok: the call's query CSR on the device; rows / list_ptr / list_of: its lists (list_of[b] = -1: no rows); qsel[0 .. n_q): the
+// queries this launch answers.  Results: the rows with a score > 0 by (score desc, row id asc), padded with id -1 / score 0.
+hipError_t launch_bm25_rows_short(const ErhBm25RowsIndex &ix, const int32_t *q_indptr, const int32_t *q_tok, const int32_t *rows,
+                                  const int64_t *list_ptr, const int32_t *list_of, const int32_t *qsel, int n_q, int k, int32_t *out_ids,
+                                  double *out_sc, int32_t *out_len, hipStream_t st);
+hipError_t launch_bm25_rows_score(const ErhBm25RowsIndex &ix, const int32_t *q_indptr, const int32_t *q_tok, const int32_t *rows,
+                                  const int64_t *list_ptr, const int32_t *list_of, const ErhBm25RowsItem *items, int n_items,
+                                  const int64_t *span_off, double *S64, hipStream_t st);
+hipError_t launch_bm25_rows_select(const double *S64, const int64_t *span_off, const int32_t *rows, const int64_t *list_ptr,
+                                   const int32_t *list_of, const int32_t *qord, int n_q, int k, int32_t *out_ids, double *out_sc,
+                                   int32_t *out_len, hipStream_t st);
+
 }  // namespace erh

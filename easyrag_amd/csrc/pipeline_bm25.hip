@@ -141,6 +141,41 @@ int bm25_topk_dev(erh_handle *h, const int32_t *qptr_dev, const int32_t *qtok_de
     return ERH_OK;
 }
 
+// Explicit row lists (bm25_rows.hip) on the selected slot: one launch for the queries whose lists fit the LDS sort, score + select per chunk
+// of the others -- chunks follow each other on the stream, which is what orders the reuse of the span buffer.  Kernel time goes to the scan
+// class (the searches) and the merge class (the select).
+int bm25_rows_dev(erh_handle *h, const Bm25RowsPlan &P, int k, int32_t *d_ids, double *d_sc, int32_t *d_len, hipStream_t st) {
+    const Bm25State &S = h->bm[h->cur];
+    erh::ErhBm25RowsIndex ix;
+    ix.indptr = S.indptr.as<int64_t>();
+    ix.doc_ids = S.doc_ids.as<int32_t>();
+    ix.payload = S.payload.p;
+    ix.f64 = S.variant == ERH_BM25_OKAPI ? 1 : 0;
+    // the slot's skip table narrows every search to one tile of the term's postings (tile_docs is a power of two)
+    ix.tile_off = nullptr; ix.n_tab = 0; ix.tab_shift = 0;
+    if (S.tile_off.p && S.n_tiles > 0 && S.tile_docs > 0 && (S.tile_docs & (S.tile_docs - 1)) == 0) {
+        ix.tile_off = S.tile_off.as<int32_t>();
+        ix.n_tab = S.n_tiles;
+        while ((1 << ix.tab_shift) < S.tile_docs) ++ix.tab_shift;
+    }
+    const double probe_bytes = 64.0;                                      // a search touches about one cache line per token range
+    if (P.n_short > 0) {
+        ProfScope ps(h, st, ERH_K_BM25_SCAN, (double)P.short_searches * probe_bytes, 0);
+        HIPCHK(h, erh::launch_bm25_rows_short(ix, P.d_qptr, P.d_qtok, P.d_rows, P.d_ptr, P.d_of, P.d_short, P.n_short, k, d_ids, d_sc, d_len, st));
+        h->stats.bm25_rows_short += 1;
+    }
+    for (const Bm25RowsPlan::Chunk &c : P.chunks) {
+        { ProfScope ps(h, st, ERH_K_BM25_SCAN, (double)c.searches * probe_bytes, 0);
+          HIPCHK(h, erh::launch_bm25_rows_score(ix, P.d_qptr, P.d_qtok, P.d_rows, P.d_ptr, P.d_of, P.d_items + c.item0, (int)(c.item1 - c.item0),
+                                                P.d_span, h->bw_s64.as<double>(), st)); }
+        { ProfScope ps(h, st, ERH_K_BM25_MERGE, (double)c.doubles * 8, 0);
+          HIPCHK(h, erh::launch_bm25_rows_select(h->bw_s64.as<double>(), P.d_span, P.d_rows, P.d_ptr, P.d_of, P.d_long + c.q0, c.q1 - c.q0, k, d_ids,
+                                                 d_sc, d_len, st)); }
+        h->stats.bm25_rows_long += 1;
+    }
+    return ERH_OK;
+}
+
 // Upload the query CSR; returns the algorithmic posting bytes of the batch in *bytes (0 if an id is bad -> error).
 int upload_bm25_queries(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, hipStream_t st,
                         const std::vector<int64_t> &host_indptr, double *bytes, int *max_qlen,

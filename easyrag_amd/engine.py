@@ -398,6 +398,31 @@ class RetrievalEngine:
                                             self._stream(stream)))
         return ids, sc, ln
 
+    def bm25_topk_rows(self, q_indptr, q_tok, k: int, lists, list_of=None, device_out: bool = False, stream=None,
+                       slot: Optional[int] = None):
+        """Exact BM25 top-k of query b over the rows lists[list_of[b]] and nothing else (erh_bm25_topk_rows): every listed row gets its
+        library-order sum; the rows with a score > 0 are ranked by (score desc, row id asc).  Each list must be strictly ascending inside
+        [0, N of the slot).  list_of None: query b uses list b; -1: no rows.  device_out: results are final after sync()."""
+        B = int(np.asarray(q_indptr).shape[0]) - 1
+        return self.bm25_topk_rows_csr(q_indptr, q_tok, k, *self.lists_to_csr(lists, list_of, B), device_out=device_out, stream=stream,
+                                       slot=slot)
+
+    def bm25_topk_rows_csr(self, q_indptr, q_tok, k: int, ptr, rows, lo, device_out: bool = False, stream=None,
+                           slot: Optional[int] = None):
+        """bm25_topk_rows on the C entry's own tables (lists_to_csr's result): a caller that sends the same lists again builds them once."""
+        self._select(slot)
+        q_indptr = _np(q_indptr, np.int32)
+        q_tok = _np(q_tok, np.int32)
+        B = q_indptr.shape[0] - 1
+        ptr, rows, lo = _np(ptr, np.int64), _np(rows, np.int32), _np(lo, np.int32)
+        if lo.shape[0] != B:
+            raise ValueError("list_of must have one entry per query")
+        ids, sc, ln = self._outs(B, k, device_out)
+        self._check(self._lib.erh_bm25_topk_rows(self._h, _ptr(q_indptr), _ptr(q_tok), B, int(k), int(ptr.shape[0] - 1), _ptr(ptr),
+                                                 _ptr(rows), _ptr(lo), _ptr(ids), _ptr(sc), _ptr(ln), 1 if device_out else 0,
+                                                 self._stream(stream)))
+        return ids, sc, ln
+
     def bm25_scores(self, q_tok, slot: Optional[int] = None) -> np.ndarray:
         self._select(slot)
         assert self.bm25 is not None
@@ -616,6 +641,7 @@ class RetrievalEngine:
                   "dense_scan_gemv_launches", "dense_scan_tile_launches", "dense_sample_passes", "dense_tile384_nomem",
                   "dense_exhaustive_queries", "bm25_redo_segments", "dense_block_groups", "dense_grouped_launches", "bm25_mixed_launches",
                   "dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches", "dense_group_reruns",
+                  "bm25_rows_calls", "bm25_rows_short_launches", "bm25_rows_long_launches",
                   "hybrid_lazy_queries", "dense_rescored_rows_last_call")
 
     def stat(self, name: str) -> int:

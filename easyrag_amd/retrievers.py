@@ -506,6 +506,66 @@ def _by_key_set(dicts: Sequence[Optional[Dict[str, Any]]]) -> List[List[int]]:
     return out
 
 
+def _per_query_rows(rows, B: int, n: int) -> List[Optional[np.ndarray]]:
+    """`rows` (one id array for every query, or a list parallel to the queries of arrays / None) -> per query None or an ascending,
+    duplicate-free int64 array inside [0, n); the same input object gives the same array object.  Both routes normalise with this."""
+    if rows is None:
+        return [None] * B
+    seen: Dict[int, tuple] = {}
+
+    def norm(a):
+        hit = seen.get(id(a))
+        if hit is None:
+            arr = np.unique(np.asarray(a).reshape(-1).astype(np.int64))
+            if arr.size and (arr[0] < 0 or arr[-1] >= n):
+                raise ValueError(f"rows must lie in [0, {n})")
+            hit = seen[id(a)] = (a, arr)               # (a is held, so its id stays its own for the call)
+        return hit[1]
+    per_query = (isinstance(rows, (list, tuple)) and len(rows) == B
+                 and all(r is None or (hasattr(r, "__len__") and not isinstance(r, (str, bytes))) for r in rows))
+    if per_query:
+        return [None if r is None else norm(r) for r in rows]
+    one = norm(rows)
+    return [one] * B
+
+
+def _rows_lists(rows_q: Sequence[np.ndarray]):
+    """Row arrays of the queries -> (distinct lists, list_of): identical arrays, by object identity or by content, become one list."""
+    lists: List[np.ndarray] = []
+    by_id: Dict[int, int] = {}
+    by_content: Dict[tuple, int] = {}
+    list_of = np.empty(len(rows_q), np.int32)
+    for j, r in enumerate(rows_q):
+        l = by_id.get(id(r))
+        if l is None:
+            key = (r.shape[0], r.tobytes())
+            l = by_content.get(key)
+            if l is None:
+                l = by_content[key] = len(lists)
+                lists.append(r)
+            by_id[id(r)] = l
+        list_of[j] = l
+    return lists, list_of
+
+
+def _node_positions(holder, nodes, nodes_or_ids, owner: str) -> np.ndarray:
+    """Positions in `nodes` of the given positions / node objects (NodeWithScore included), ascending and distinct.  The object ->
+    position map is built on first use and kept on `holder`."""
+    where = holder.__dict__.get("_position")
+    ids = []
+    for x in nodes_or_ids:
+        if isinstance(x, (int, np.integer)):
+            ids.append(int(x))
+            continue
+        if where is None:
+            where = holder.__dict__["_position"] = {id(n): i for i, n in enumerate(nodes)}
+        node = getattr(x, "node", x)
+        if id(node) not in where:
+            raise ValueError(f"score_nodes: a node that is not part of this {owner}'s node list")
+        ids.append(where[id(node)])
+    return np.unique(np.asarray(ids, np.int64))
+
+
 def _corpus_for(nodes, engine: Optional[RetrievalEngine]) -> _FilteredCorpus:
     """Retrievers built over the same engine share one _FilteredCorpus (and so one metadata upload).  The
     bookkeeping lives on the engine object (no process-global cache pinning engines); an engine serves ONE node
@@ -759,26 +819,7 @@ class HipVectorStore:
         return ids, sc, ln
 
     def _per_query_rows(self, rows, B: int) -> List[Optional[np.ndarray]]:
-        """`rows` -> per query None or an ascending, duplicate-free int64 array; the same input object gives the same array object."""
-        if rows is None:
-            return [None] * B
-        n = len(self.corpus.nodes)
-        seen: Dict[int, tuple] = {}
-
-        def norm(a):
-            hit = seen.get(id(a))
-            if hit is None:
-                arr = np.unique(np.asarray(a).reshape(-1).astype(np.int64))
-                if arr.size and (arr[0] < 0 or arr[-1] >= n):
-                    raise ValueError(f"rows must lie in [0, {n})")
-                hit = seen[id(a)] = (a, arr)               # (a is held, so its id stays its own for the call)
-            return hit[1]
-        per_query = (isinstance(rows, (list, tuple)) and len(rows) == B
-                     and all(r is None or (hasattr(r, "__len__") and not isinstance(r, (str, bytes))) for r in rows))
-        if per_query:
-            return [None if r is None else norm(r) for r in rows]
-        one = norm(rows)
-        return [one] * B
+        return _per_query_rows(rows, B, len(self.corpus.nodes))
 
     def _resolve_rows(self, dicts, rows, B: int, mode: int):
         """Per query the rows it may rank (None: it runs through today's filter paths) and the filters left for those paths.  A query
@@ -821,24 +862,7 @@ class HipVectorStore:
                         dicts[b] = None
         return rows_q, dicts
 
-    @staticmethod
-    def _rows_lists(rows_q: Sequence[np.ndarray]):
-        """Row arrays of the queries -> (distinct lists, list_of): identical arrays, by object identity or by content, become one list."""
-        lists: List[np.ndarray] = []
-        by_id: Dict[int, int] = {}
-        by_content: Dict[tuple, int] = {}
-        list_of = np.empty(len(rows_q), np.int32)
-        for j, r in enumerate(rows_q):
-            l = by_id.get(id(r))
-            if l is None:
-                key = (r.shape[0], r.tobytes())
-                l = by_content.get(key)
-                if l is None:
-                    l = by_content[key] = len(lists)
-                    lists.append(r)
-                by_id[id(r)] = l
-            list_of[j] = l
-        return lists, list_of
+    _rows_lists = staticmethod(_rows_lists)        # (the module-level helper both routes share)
 
     def _query_filtered(self, q, k: int, dicts, mode: int):
         """The batch through the filter paths: class column, class sets, one device column per metadata key set."""
@@ -943,19 +967,7 @@ class QdrantRetriever(_RetrieverBase):
         the embedding: the dense twin of BM25Retriever.get_scores(query, docs).  Every node gets its exact score on the device (one
         call, the nodes in lists of at most 768, the call's limit on k); (score desc, position asc); `top_k` cuts the result."""
         store = self._vector_store
-        where = store.__dict__.get("_position")
-        ids = []
-        for x in nodes_or_ids:
-            if isinstance(x, (int, np.integer)):
-                ids.append(int(x))
-                continue
-            if where is None:
-                where = store.__dict__["_position"] = {id(n): i for i, n in enumerate(store.nodes)}
-            node = getattr(x, "node", x)
-            if id(node) not in where:
-                raise ValueError("score_nodes: a node that is not part of this store's node list")
-            ids.append(where[id(node)])
-        ids = np.unique(np.asarray(ids, np.int64))
+        ids = _node_positions(store, store.nodes, nodes_or_ids, "store")
         if ids.size == 0:
             return []
         chunks = [ids[i:i + DENSE_MAX_K] for i in range(0, ids.size, DENSE_MAX_K)]
@@ -1075,15 +1087,21 @@ class BM25Retriever(_RetrieverBase):
         metadata key does not match (the reference raises KeyError there)."""
         return self._filter_one(scores, self.filter_dict, self._similarity_top_k)
 
-    def _filter_one(self, scores: np.ndarray, filter_dict, top_k: int) -> List[NodeWithScore]:
+    def _filter_one(self, scores: np.ndarray, filter_dict, top_k: int, rows: Optional[np.ndarray] = None) -> List[NodeWithScore]:
+        """`rows`: node positions the walk may keep (None: all); a node outside them is rejected like one the filter rejects."""
         scores = np.asarray(scores)
         order = np.lexsort((np.arange(scores.shape[0]), -scores.astype(np.float64)))
+        keep = None
+        if rows is not None:
+            keep = np.zeros(scores.shape[0], bool)
+            keep[rows] = True
         out: List[NodeWithScore] = []
         for ix in order:
             if scores[ix] <= 0:
                 break
             meta = self._nodes[ix].metadata
-            if filter_dict is None or not any(k not in meta or meta[k] != v for k, v in filter_dict.items()):
+            if (keep is None or keep[ix]) and (
+                    filter_dict is None or not any(k not in meta or meta[k] != v for k, v in filter_dict.items())):
                 out.append(NodeWithScore(node=self._nodes[ix], score=float(scores[ix])))
             if len(out) == top_k:
                 break
@@ -1094,27 +1112,75 @@ class BM25Retriever(_RetrieverBase):
             logger.warning("BM25Retriever does not support embeddings, skipping...")
         return self.retrieve_batch([query_bundle.query_str])[0]
 
-    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET) -> List[List[NodeWithScore]]:
+    def _resolve_rows(self, dicts, rows, B: int):
+        """Per query the rows it may rank (None: it runs through the class-column call) and the filters left for that call.  A query with
+        rows AND a filter_dict keeps the rows that pass the filter: a host lookup in the class column over the filter's keys."""
+        rows_q = _per_query_rows(rows, B, len(self._nodes))
+        dicts = list(dicts)
+        for b in range(B):
+            if rows_q[b] is not None and dicts[b]:
+                c = self._corpus_state.filter_class(dicts[b])          # (32767: no document carries these values)
+                r = rows_q[b]
+                rows_q[b], dicts[b] = r[self._corpus_state._classes.ids[r] == c], None
+        return rows_q, dicts
+
+    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, rows=None) -> List[List[NodeWithScore]]:
         """get_scores + filter for a whole batch, fused on the GPU (no score vector leaves the chip).  `filter_dicts`
-        (default: the `filter_dict` attribute, for every query) may be a list parallel to `queries`: one dict / None each."""
+        (default: the `filter_dict` attribute, for every query) may be a list parallel to `queries`: one dict / None each.
+        `rows`: restrict queries to explicit node positions -- one id array for every query, or a list parallel to the queries whose
+        entries are an id array or None (HipVectorStore.query_batch's argument, normalised the same way).  Such a query ranks exactly
+        those rows by the corpus index's BM25 (erh_bm25_topk_rows; with a filter_dict as well: the rows that also pass it), the others
+        run as without the argument, and the two parts are scattered into one result."""
         B = len(queries)
         if B == 0:
             return []
         dicts = _per_query(self.filter_dict if filter_dicts is _UNSET else filter_dicts, B, lambda v: dict(v) if v else None)
         tok = [self._query_ids(q) for q in queries]
         k = self._similarity_top_k
+        rows_q, dicts = self._resolve_rows(dicts, rows, B)
         if not 1 <= k <= BM25_DEVICE_MAX_K:
             # outside the fused kernels' range (erh_bm25_topk: 1 <= k <= 1024) the reference's answer is still defined: the
-            # score vector plus the host filter give it exactly
-            return [self._filter_one(self._cast(self.engine.bm25_scores(t, slot=self._slot)), d, k) for t, d in zip(tok, dicts)]
+            # score vector plus the host filter (restricted to the rows) give it exactly
+            return [self._filter_one(self._cast(self.engine.bm25_scores(t, slot=self._slot)), d, k, rows=r)
+                    for t, d, r in zip(tok, dicts, rows_q)]
         out: List[List[NodeWithScore]] = [[] for _ in range(B)]
-        for g in _by_key_set(dicts):
+        rest = [b for b in range(B) if rows_q[b] is None]
+        for g in _by_key_set([dicts[b] for b in rest]):
+            g = [rest[j] for j in g]
             qi, qt = queries_to_csr([tok[b] for b in g])
             ids, sc, ln = self.engine.bm25_topk(qi, qt, self._similarity_top_k, slot=self._slot,
                                                 filter_dir=self._corpus_state.filter_column([dicts[b] for b in g]))
             for j, b in enumerate(g):
                 out[b] = [NodeWithScore(node=self._nodes[i], score=float(s)) for i, s in zip(ids[j, :ln[j]], sc[j, :ln[j]])]
+        with_rows = [b for b in range(B) if rows_q[b] is not None]
+        if with_rows:
+            lists, list_of = _rows_lists([rows_q[b] for b in with_rows])
+            qi, qt = queries_to_csr([tok[b] for b in with_rows])
+            ids, sc, ln = self.engine.bm25_topk_rows(qi, qt, k, lists, list_of=list_of, slot=self._slot)
+            for j, b in enumerate(with_rows):
+                out[b] = [NodeWithScore(node=self._nodes[i], score=float(s)) for i, s in zip(ids[j, :ln[j]], sc[j, :ln[j]])]
         return out
+
+    def score_nodes(self, query: str, nodes_or_ids, top_k: Optional[int] = None) -> List[NodeWithScore]:
+        """The given nodes -- positions in the node list, or node objects of it (NodeWithScore included) -- and nothing else, ranked by
+        the CORPUS index's BM25: the sparse twin of QdrantRetriever.score_nodes.  Every node gets its exact score on the device (one
+        call, the nodes in lists of at most 1024, the call's limit on k); only nodes with a score > 0 are returned, as everywhere on
+        this route; (score desc, position asc); `top_k` cuts the result.
+        Not get_scores(query, docs): that one builds a throw-away index over the given strings, so its idf and avgdl are THEIRS and a
+        score there depends on which other strings were passed; here idf, avgdl and document lengths are the corpus's, and a node's
+        score is the one retrieve() would report for it."""
+        ids = _node_positions(self, self._nodes, nodes_or_ids, "retriever")
+        if ids.size == 0:
+            return []
+        chunks = [ids[i:i + BM25_DEVICE_MAX_K] for i in range(0, ids.size, BM25_DEVICE_MAX_K)]
+        qi, qt = queries_to_csr([self._query_ids(query)] * len(chunks))
+        got, sc, ln = self.engine.bm25_topk_rows(qi, qt, len(chunks[0]), chunks, slot=self._slot)
+        got = np.concatenate([got[j, :ln[j]] for j in range(len(chunks))])
+        sc = np.concatenate([sc[j, :ln[j]] for j in range(len(chunks))])
+        order = np.lexsort((got, -sc))                     # (one chunk: already in this order)
+        if top_k is not None:
+            order = order[:max(int(top_k), 0)]
+        return [NodeWithScore(node=self._nodes[int(got[i])], score=float(sc[i])) for i in order]
 
 
 _SCRATCH_LOCK = threading.Lock()
@@ -1263,24 +1329,28 @@ class HybridRetriever(_RetrieverBase):
         """Route selection + filter push-down + RRF (retrievers.py:276-291)."""
         return self.retrieve_batch([query_bundle.query_str])[0]
 
-    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, filters=_UNSET, rows=None) -> List[List[NodeWithScore]]:
+    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, filters=_UNSET, rows=None,
+                       sparse_rows=None) -> List[List[NodeWithScore]]:
         """`_aretrieve` for a batch of query strings.  Without the keyword arguments the `filter_dict` / `filters`
         attributes apply to every query and are pushed into the child retrievers as the reference does
         (retrievers.py:278,283).  `filter_dicts` (sparse route) / `filters` (dense route) may instead be lists parallel to
         `queries` -- the reference's evaluation loop changes both before every question (pipeline.py:301-312,331-341), so a
         batch of its questions needs one filter per query; the child retrievers' attributes are left alone then.
-        `rows` restricts the DENSE route (QdrantRetriever.retrieve_batch's argument); the sparse route keeps its filter_dict."""
+        `rows` restricts the DENSE route (QdrantRetriever.retrieve_batch's argument); the sparse route keeps its filter_dict.
+        `sparse_rows` restricts the SPARSE route (BM25Retriever.retrieve_batch's `rows`); the same object passed as both holds the
+        fused call to one id set: RRF then runs on two lists drawn from the same population."""
         sp, de = self.sparse_retriever, self.dense_retriever
         B = len(queries)
         if B == 0:
             return []
         fs = self.filter_dict if filter_dicts is _UNSET else filter_dicts
         fdn = self.filters if filters is _UNSET else filters
+        s_kw = {} if sparse_rows is None else {"rows": sparse_rows}
         if self.retrieval_type != 1:
             if filter_dicts is _UNSET:
                 sp.filter_dict = self.filter_dict
             if self.retrieval_type == 2:
-                return sp.retrieve_batch(queries, filter_dicts=fs)
+                return sp.retrieve_batch(queries, filter_dicts=fs, **s_kw)
         if self.retrieval_type != 2:
             if filters is _UNSET:
                 de.filters = self.filters
@@ -1292,9 +1362,17 @@ class HybridRetriever(_RetrieverBase):
         key_sets = {_spec_keys(fd) for fd in d_sparse + d_dense if _spec_keys(fd)}
         if not self._fused_possible() or len(key_sets) > 1 or not self._fused_sizes():
             # (outside erh_hybrid_topk's sizes the routes run on their own: each one falls back or names its limit)
-            sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs), de.retrieve_batch(queries, filters=fdn, rows=rows)
+            sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs, **s_kw), de.retrieve_batch(queries, filters=fdn, rows=rows)
             return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
         vs = de._vector_store
+        if sparse_rows is not None:
+            s_rows_q, _ = sp._resolve_rows(d_sparse, sparse_rows, B)
+            rows_q, _ = vs._resolve_rows(d_dense, rows, B, _lib.ERH_DENSE_EXACT)
+            if all(r is not None for r in s_rows_q) and all(r is not None for r in rows_q):
+                return self._retrieve_rows(queries, d_sparse, rows_q, s_rows_q)
+            # any mixture of rows and non-rows queries on either route: the routes on their own + RRF
+            sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs, **s_kw), de.retrieve_batch(queries, filters=fdn, rows=rows)
+            return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
         if rows is not None or any(sp and _spec_keys(sp) and vs.corpus.too_many_values(_spec_keys(sp)) for sp in d_dense):
             rows_q, _ = vs._resolve_rows(d_dense, rows, B, _lib.ERH_DENSE_EXACT)
             if any(r is None for r in rows_q):         # a batch that mixes rows and non-rows dense queries: the routes on their own + RRF
@@ -1338,18 +1416,23 @@ class HybridRetriever(_RetrieverBase):
         return [[NodeWithScore(node=nodes[i], score=float(s)) for i, s in zip(ids[b, :ln[b]], sc[b, :ln[b]])]
                 for b in range(B)]
 
-    def _retrieve_rows(self, queries: Sequence[str], d_sparse, rows_q) -> List[List[NodeWithScore]]:
-        """retrieval_type 3 with explicit rows on the dense side, every step on the device: BM25 top-k (class column of filter_dict) and
-        erh_dense_topk_rows into device buffers, the RRF kernel over the two device lists, one synchronisation (the rows entry leaves
-        nothing for erh_dense_check)."""
+    def _retrieve_rows(self, queries: Sequence[str], d_sparse, rows_q, s_rows_q=None) -> List[List[NodeWithScore]]:
+        """retrieval_type 3 with explicit rows on the dense side, every step on the device: BM25 top-k (class column of filter_dict; with
+        `s_rows_q`, the sparse route's own row lists with its filter already applied: erh_bm25_topk_rows) and erh_dense_topk_rows into
+        device buffers, the RRF kernel over the two device lists, one synchronisation (the rows entries leave nothing for
+        erh_dense_check)."""
         sp, de = self.sparse_retriever, self.dense_retriever
         eng, cstate = sp.engine, sp._corpus_state
         B = len(queries)
-        filt_s = cstate.filter_column(d_sparse)
         lists, list_of = de._vector_store._rows_lists(rows_q)
         qi, qt = queries_to_csr([sp._query_ids(q) for q in queries])
         embs = _unit_f16(np.asarray([de._embed_model.get_query_embedding(q) for q in queries], dtype=np.float32))
-        sids, _, sln = eng.bm25_topk(qi, qt, sp._similarity_top_k, filter_dir=filt_s, device_out=True, slot=sp._slot)
+        if s_rows_q is None:
+            filt_s = cstate.filter_column(d_sparse)
+            sids, _, sln = eng.bm25_topk(qi, qt, sp._similarity_top_k, filter_dir=filt_s, device_out=True, slot=sp._slot)
+        else:
+            s_lists, s_list_of = _rows_lists(s_rows_q)
+            sids, _, sln = eng.bm25_topk_rows(qi, qt, sp._similarity_top_k, s_lists, list_of=s_list_of, device_out=True, slot=sp._slot)
         dids, _, dln = eng.dense_topk_rows(embs, de._similarity_top_k, lists, list_of=list_of, device_out=True)
         fids, fsc, fln = eng.rrf_device(sids, sln, dids, dln, K=60, topk=self.topk)
         eng.sync()

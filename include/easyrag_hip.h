@@ -36,6 +36,8 @@
  *                        retrievers.py:44-47): explicit row lists, exact by scoring every listed row
  *   erh_bm25_scores      BM25Retriever.get_scores (retrievers.py:128-151)
  *   erh_bm25_topk        BM25Retriever._retrieve = get_scores + filter (retrievers.py:191-220)
+ *   erh_bm25_topk_rows   the same where the filter's keep mask is an explicit id set per query (retrievers.py:128-151, 191-210): every listed
+ *                        row scored exactly, no scan of the postings
  *   erh_rrf              HybridRetriever.reciprocal_rank_fusion (retrievers.py:256-274)
  *   erh_fusion           HybridRetriever.fusion (retrievers.py:239-253)
  *   erh_hybrid_topk      HybridRetriever._aretrieve, retrieval_type == 3 (retrievers.py:276-291)
@@ -251,6 +253,27 @@ int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_devi
 int erh_bm25_topk(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
                   const int16_t *filter_dir,
                   int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
+
+/* BM25 top-k where each query ranks an EXPLICIT LIST OF ROWS and nothing else: what BM25Retriever.get_scores + .filter return
+ * (src/easyrag/custom/retrievers.py:128-151, 191-210) when the keep mask is an id set -- a dir of a few hundred chunks, an ACL's ids, a
+ * candidate list to re-score, a session's ids -- and the sparse twin of erh_dense_topk_rows.  Acts on the slot chosen by erh_bm25_select.
+ *   Queries as for erh_bm25_topk (host CSR of term ids in [0, V); an empty query gives out_len[b] = 0).  Lists as for erh_dense_topk_rows:
+ *   list_ptr int64[n_lists+1], list_rows int32[list_ptr[n_lists]] (host CSR), row ids strictly ascending in [0, N of the slot); list_ptr[0] = 0,
+ *   non-decreasing; list_of host int32[B]: the list of query b, -1 = no rows.  Anything else: ERH_ERR_INVALID, checked on the host before
+ *   anything is enqueued (outputs untouched).  k outside [1, 1024]: ERH_ERR_UNSUPPORTED; no index in the slot: ERH_ERR_STATE; work space that
+ *   cannot be allocated: ERH_ERR_NOMEM.
+ * Score: the one of erh_set_bm25_csr -- the payloads of the query's terms in query order, repeats included, summed from 0 in the payload's
+ * type, an absent term adding + 0 -- for EVERY listed row, so there is no threshold and nothing to verify; indices with payloads of either
+ * sign work alike.  Result for query b: its rows with score > 0 (retrievers.py:195-196) under (score descending, row id ascending), the
+ * first k; scores as float64 (float32 sums widened exactly); padded with id -1, score 0; out_len[b] = min(k, number of positive rows).
+ * Host outputs are final on return, device outputs after erh_sync.  The call sets no flag words (erh_dense_check has nothing to do on its
+ * account) and keeps to buffers of its own: enqueued behind a device-output erh_bm25_topk / erh_dense_topk / erh_dense_topk_rows on the same
+ * stream it leaves that call's results intact.
+ * Option bm25_rows_ws_mb (256): score work space of lists longer than 2048 rows, at least one list of N rows; a call that needs more runs in
+ * chunks of queries, one behind the other on the stream. */
+int erh_bm25_topk_rows(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
+                       int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
+                       int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
 
 /* Dense score vector of one query (host int32[n_tok]) over all N documents: float64[N] on the host
  * (float32 sums widened exactly for ERH_BM25_BM25S).  Mirrors BM25Retriever.get_scores. */
@@ -515,6 +538,9 @@ int erh_dense_exhaustive_count(erh_handle *h, int32_t *count);
  *                                                      device counter, summed over calls)
  *   dense_rows_calls                                   erh_dense_topk_rows calls
  *   dense_rows_short_launches / dense_rows_long_launches  its launches of the short shape (one workgroup per query, lists of at most 2048 rows) /
+ *                                                      of the long shape (one score + select pair per chunk of queries)
+ *   bm25_rows_calls                                    erh_bm25_topk_rows calls
+ *   bm25_rows_short_launches / bm25_rows_long_launches    its launches of the short shape (one workgroup per query, lists of at most 2048 rows) /
  *                                                      of the long shape (one score + select pair per chunk of queries)
  *   bm25_mixed_launches                                BM25 scans launched with both bodies (bm25_mixed: a batch with queries longer than bm25_long_tokens)
  *   bm25_redo_segments                                 (query, segment) pairs the fixed-point scan handed to the exact block scan (device counter)
