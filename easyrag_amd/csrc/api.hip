@@ -404,6 +404,19 @@ int erh_set_dense(erh_handle *h, const void *x, int64_t n, int d, int dtype, int
     // The norm went through the flag words, and the matrix the last dense call scanned is gone: nothing of that call is left for
     // erh_dense_check to read (it would take the norm's bits for a flagged query and the old matrix for the exhaustive path's).
     h->forget_dense_call();
+    if (!(xn <= 3.4028235e38f)) {
+        // An fp16 Inf / NaN, or an fp32 value that converts to Inf: the margin would be infinite and nothing could be pruned or certified.
+        // The old matrix is overwritten already, so the handle is left without one, as before any erh_set_dense.
+        h->X.release();
+        h->Xt.release();
+        h->xt_valid = false;
+        h->N = 0;
+        h->d = 0;
+        h->pos_mul = h->pos_inv = 1;
+        h->xnorm_max = 0.f;
+        h->view_global();
+        return h->fail(ERH_ERR_INVALID, "erh_set_dense: non-finite row (an fp16 Inf / NaN, or an fp32 value that converts to one)");
+    }
     h->xnorm_max = xn;
     h->N = n;
     h->d = d;

@@ -63,7 +63,9 @@ __global__ __launch_bounds__(256) void prep_queries_kernel(const TIN *__restrict
     }
     float s2 = 0.f;
     for (int i = threadIdx.x; i < d; i += 256) {
-        const _Float16 hv = (_Float16)((float)in[i] * inv);
+        float pv = (float)in[i] * inv;
+        asm("" : "+v"(pv));                                           // (see convert_rows_kernel: keeps the sign of a -0.0 element)
+        const _Float16 hv = (_Float16)pv;
         out[i] = hv;
         const float f = (float)hv;
         s2 += f * f;
@@ -87,7 +89,15 @@ __global__ __launch_bounds__(256) void convert_rows_kernel(const float *__restri
             ss = block_sum_256(ss, red);
             inv = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
         }
-        for (int i = threadIdx.x; i < d; i += 256) out[i] = (_Float16)(in[i] * inv);
+        for (int i = threadIdx.x; i < d; i += 256) {
+            // The product is rounded to fp32, then ONCE to fp16 (round to nearest even, subnormals kept: numpy's astype).  The empty asm
+            // keeps the compiler from folding multiply and conversion into v_fma_mixlo_f16 with a +0 addend, which turns -0.0 into +0.0
+            // (LLVM's AMDGPU selection of fptrunc(fmul a, b) as mixlo(a, b, src2 = +0); with src2 = -0 the fold would be exact and the
+            // barrier could go -- test_fp32_rows_and_queries_round_like_numpy guards either way).
+            float pv = in[i] * inv;
+            asm("" : "+v"(pv));
+            out[i] = (_Float16)pv;
+        }
     }
 }
 
@@ -132,8 +142,10 @@ __global__ __launch_bounds__(256) void row_norm_max_kernel(const _Float16 *__res
         float ss = 0.f;
         for (int i = threadIdx.x; i < d; i += 256) { const float v = (float)in[i]; ss += v * v; }
         ss = block_sum_256(ss, red);
+        if (!(ss <= 3.4028235e38f)) ss = INFINITY;                   // a row with an Inf or a NaN: fmaxf would drop the NaN
         best = fmaxf(best, ss);
     }
+    // (the bits of +inf are above those of every finite norm: one non-finite row makes the result +inf, which erh_set_dense refuses)
     if (threadIdx.x == 0) atomicMax((unsigned int *)out, __float_as_uint(sqrtf(best) * 1.0001f));
 }
 

@@ -90,7 +90,11 @@ int         erh_sync(erh_handle *h, void *stream);
 /* Chunk-embedding matrix, row-major [n x d], d % 64 == 0.  dtype ERH_F16 rows are taken as they
  * are; ERH_F32 rows are converted to fp16 on the device.  normalize != 0 L2-normalises each row
  * (in fp32) before the fp16 rounding, which is what Qdrant does at insert for Distance.COSINE.
- * The handle keeps its own device copy. */
+ * The handle keeps its own device copy.
+ * Input domain: every stored fp16 value is finite; any row norm, subnormal fp16 values, signed zeros and all-zero rows are
+ * allowed and are scored as the numbers they are.  A row that holds an fp16 Inf or NaN, or an fp32 value that converts to one
+ * (|v| >= 65520 with normalize = 0), is refused: ERH_ERR_INVALID ("non-finite row"), and the handle is left WITHOUT a chunk
+ * matrix -- a dense call then fails with ERH_ERR_STATE as before any erh_set_dense, and a later valid erh_set_dense works. */
 int erh_set_dense(erh_handle *h, const void *x, int64_t n, int d, int dtype, int is_device_ptr, int normalize);
 
 /* Read rows [row0, row0 + rows) of the stored chunk matrix back in the CALLER's order (fp16, as stored): what
@@ -206,7 +210,10 @@ int     erh_text_encode_mt(const erh_cutter *c, erh_vocab *v, const erh_vocab *s
 
 /* Dense top-k for B queries.  q is [B x d] (ERH_F16 or ERH_F32, host or device); normalize_q != 0
  * L2-normalises each query.  filter_dir: host int16[B], -1 = unfiltered, or NULL.
- * out_ids int32[B*k], out_scores float64[B*k], out_len int32[B] (all host or all device). */
+ * out_ids int32[B*k], out_scores float64[B*k], out_len int32[B] (all host or all device).
+ * Input domain of the queries (every dense entry point): finite values of any norm; subnormal fp16 values, signed zeros and an
+ * all-zero query (every score is 0: the first k allowed rows in index order) are allowed.  A query that holds an Inf or a NaN
+ * is not refused: its ranking is unspecified (memory safety is not affected). */
 int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
                    int B, int k, const int16_t *filter_dir, int mode,
                    int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);

@@ -78,7 +78,9 @@ def bands(e_allowed: np.ndarray, tau: float, delta: float, k: int) -> dict:
     tau = float(tau)
     kth = kth_score(e_allowed, k)
     lvl = tau + 2.0 * delta
-    lvl = lvl + abs(lvl) * 1e-6 if np.isfinite(lvl) else lvl            # (equals (tau + 2 delta)(1 + 1e-6) for the positive levels of real data)
+    # the device's own nudge, lvl += |lvl| * 1e-6: UP for either sign ((tau + 2 delta)(1 + 1e-6) for a positive level, (1 - 1e-6) for a
+    # negative one), none at a level of zero -- test_gpu_dense_numerics.py exercises negative and zero levels
+    lvl = lvl + abs(lvl) * 1e-6 if np.isfinite(lvl) else lvl
     return {"L": int(np.count_nonzero(e_allowed >= tau + dh)), "U": int(np.count_nonzero(e_allowed >= tau - dh)),
             "n_hi": int(np.count_nonzero(e_allowed >= lvl + dh)), "n_lo": int(np.count_nonzero(e_allowed >= lvl - dh)),
             "W": int(np.count_nonzero(e_allowed >= kth - 4.0 * dh)), "kth": kth, "dh": dh, "verifiable": bool(np.isfinite(lvl))}

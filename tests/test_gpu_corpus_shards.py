@@ -78,6 +78,38 @@ def test_shard_merge_reads_the_rows_erh_pack_topk_writes(engine):
     _same(_cpu(got), merge_batch(ids, sc, ln, base, k))
 
 
+def test_shard_merge_of_short_lists_with_negative_scores(engine):
+    """Three slices whose lists are all shorter than k and hold negative scores only (dense scores of a query that points away from the
+    corpus): the padding entries of the packed rows carry (id -1, score 0.0), which would outrank every live entry if the merge took one for
+    a row.  erh_pack_topk writes the rows; the merged lists (shorter than k too: padded again) equal the numpy merge."""
+    import torch
+    rng = np.random.default_rng(58)
+    world, B, k, rows = 3, 13, 100, 700
+    ids = np.full((world, B, k), -1, np.int32)
+    sc = np.zeros((world, B, k), np.float64)
+    ln = np.zeros((world, B), np.int32)
+    levels = -(rng.random(5) + 0.25)
+    for r in range(world):
+        for q in range(B):
+            n = int(rng.integers(0, 30)) if q else 0                                    # (query 0: empty on every rank)
+            loc = rng.choice(rows, size=n, replace=False).astype(np.int64)
+            s = levels[rng.integers(0, 5, size=n)] if q % 2 else -(rng.random(n) + 1e-3)   # equal bits across ranks / distinct scores
+            order = np.lexsort((loc, -s))
+            ids[r, q, :n], sc[r, q, :n], ln[r, q] = loc[order], s[order], n
+    assert ln.sum(axis=0).max() < k and np.all(sc <= 0.0)
+    recv = torch.empty((world, B, engine.topk_row_bytes(k)), dtype=torch.uint8, device="cuda")
+    for r in range(world):
+        engine.pack_topk(_dev(ids[r]), _dev(sc[r]), _dev(ln[r]), recv[r])
+    base = np.arange(world, dtype=np.int32) * rows
+    got = engine.shard_merge_topk(recv, B, world, k, base)
+    torch.cuda.synchronize()
+    got = _cpu(got)
+    want = merge_batch(ids, sc, ln, base, k)
+    _same(got, want)
+    for q in range(B):
+        assert got[2][q] == ln[:, q].sum() and np.all(got[0][q, :got[2][q]] >= 0) and np.all(got[1][q, :got[2][q]] < 0.0), q
+
+
 @pytest.mark.parametrize("world", [1, 3, 8])
 @pytest.mark.parametrize("k_sparse,k_dense", [(192, 288), (1024, 768), (1, 1), (1024, 10)])
 def test_shard_rrf_kernel_equals_merge_then_oracle_rrf(engine, k_sparse, k_dense, world):
