@@ -248,12 +248,9 @@ hipError_t dense_gemv_init() {
 
 // hipErrorInvalidValue when the shape does not qualify (more than 64 queries, d not a multiple of 32, query
 // fragments larger than LDS): the caller then uses the padded MFMA scan.
-hipError_t launch_dense_gemv_append(const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Q, int B,
-                                    const float *tau, const int16_t *filter_dir, const int16_t *dir_id, ErhCand *cand,
-                                    uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus, int kb, int wgs, int pipe,
-                                    hipStream_t st, int nt) {
-    return gemv_launch(false, X, N, d, c0, c1, Q, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, nullptr, 0,
-                       n_cus, kb, wgs, pipe, st, nt);
+hipError_t launch_dense_gemv_append(const ErhScanArgs &a, int n_cus, int kb, int wgs, int pipe, hipStream_t st, int nt) {
+    return gemv_launch(false, a.X, a.N, a.d, a.c0, a.c1, a.Q, a.B, a.tau, a.filter_dir, a.dir_id, a.cand, a.cand_cnt, a.cap, a.overflow,
+                       nullptr, 0, n_cus, kb, wgs, pipe, st, nt);
 }
 
 // Seed prefix of the same small batch: S0[q][chunk - c0] for chunks [c0, c0 + nc), q < B.

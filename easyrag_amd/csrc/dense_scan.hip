@@ -590,7 +590,7 @@ __device__ __forceinline__ float erh_max4(float a, float b, float c, float d) {
 // (s, s+1) of one operand = the two 64-byte halves of the same 128-byte lines, issued back to back so that the second half
 // hits in L1.  Used by dense_scan_pp3_kernel (and by the lean kernel of the measurement builds).
 #define ERH_PP2_GLDS(SRC, DST) __builtin_amdgcn_global_load_lds((const void *)(SRC), ERH_LDS_PTR(DST), 16, 0, 0)
-// the chunk side: kPpAuxX is a constant of the kernel that expands the macro -- 2 = the non-temporal hint (dense_scan_pp3_kernel VAR bit 6:
+// the chunk side: kPpAuxX is a constant of the kernel that expands the macro -- 2 = the non-temporal hint (dense_scan_pp3_kernel VAR kPp3NtX:
 // a launch in which every chunk row is read by ONE workgroup, i.e. one query tile per matrix), 0 = the default policy
 #define ERH_PP2_GLDS_X(SRC, DST) __builtin_amdgcn_global_load_lds((const void *)(SRC), ERH_LDS_PTR(DST), 16, 0, kPpAuxX)
 #define ERH_PP2_ISSUE_A()                                                                             \
@@ -636,11 +636,13 @@ __device__ __forceinline__ float erh_max4(float a, float b, float c, float d) {
 // PABL (measurement builds only, -DERH_MEASURE): bit mask -- 1 no epilogue, 2 thresholds forced to +inf, 4 no MFMA,
 // 8 no chunk-side DMA, 16 no query-side DMA, 32 no fragment reads, 64 phase clocks.  Anything but 0 and 64 gives
 // invalid results.  The option "dense_ablate" keeps its round-1 codes (pp_mask_of below maps them).
-#ifdef ERH_MEASURE
-constexpr int kPp3LockStep = 1;    // VAR bit 0 of dense_scan_pp3_kernel (DMA inside the matrix segment, one barrier per stage)
-#else
-constexpr int kPp3LockStep = 0;    // ... a measured dead end: not in the product build
-#endif
+// VAR of dense_scan_pp3_kernel: what one instantiation is specialised for.  Which combinations exist is ERH_PP3_VARIANTS, below.
+constexpr int kPp3LockStep = 1;    // DMA inside the matrix segment, one barrier per stage: a measured dead end, measurement builds only
+constexpr int kPp3Tiled = 2;       // the chunk operand is the tiled copy (dense_tile_rows_kernel), c0 % 256 == 0
+constexpr int kPp3HalfQ = 8;       // half query tile: at most 128 queries, the other half of the tile is not computed
+constexpr int kPp3Seed = 16;       // the sample pass: no thresholds, the two best scores of every cell (kernels.h: ErhSeedIo)
+constexpr int kPp3Grouped = 32;    // one matrix per query tile (kernels.h: ErhGroupIo)
+constexpr int kPp3NtX = 64;        // chunk-side loads with the non-temporal hint: every chunk row has one reader
 constexpr int kPpNoEpi = 1, kPpTauInf = 2, kPpNoMfma = 4, kPpNoDmaA = 8, kPpNoDmaB = 16, kPpNoFrag = 32, kPpClocks = 64;
 #ifdef ERH_MEASURE   // the first two generations of the ping-pong scan (dense_scan_pp_kernel, dense_scan_pp2_kernel): csrc/measure/dense_scan_pp12.inc
 #include "measure/dense_scan_pp12.inc"
@@ -689,7 +691,7 @@ __global__ __launch_bounds__(256) void dense_tile_rows_kernel(const _Float16 *__
 // for its pieces of stage g+1 (after M_h everything but the youngest 4 (h even) / 8 (h odd) instructions has landed),
 // and M_h overwrites the ring slots of stages h-1 and h, whose last reads (C(h-1)) retired before |B| of stage h-1
 // (lgkmcnt(0) ahead of every |B|).
-// GROUPED (VAR bit 5; round 6): ONE launch serves several matrices.  Every 256-row query tile has its own matrix (a dir's block copy,
+// GROUPED (VAR kPp3Grouped; round 6): ONE launch serves several matrices.  Every 256-row query tile has its own matrix (a dir's block copy,
 // kernels.h: ErhDenseView) and its own set of chunk streams: workgroup b belongs to query tile gio.wg_view[b] and is stream
 // b - wg0 of that tile's nwg streams, scanning rows [n0, N) of the tile's matrix.  Everything behind the prologue -- rings, segments,
 // epilogue, records -- is the ordinary kernel's; the (X, N, c0, c1) arguments and the block -> (query tile, stream) map are what the table
@@ -702,13 +704,13 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp3_kernel(
     ErhCand *__restrict__ cand, uint32_t *__restrict__ cand_cnt, int cap, uint32_t *__restrict__ overflow,
     unsigned long long *__restrict__ dbg /* kPpClocks only */, int rot_stages,
     uint32_t *__restrict__ stream_sync /* one zeroed word per stream, or null: see ERH_PP3_STREAM_SYNC */,
-    const erh::ErhSeedIo sio /* VAR bit 4: this launch is the sample pass (kernels.h) */,
-    const erh::ErhGroupIo gio /* VAR bit 5 */) {
-    constexpr bool GROUPED = (VAR & 32) != 0;
-    constexpr int kPpAuxX = (VAR & 64) ? 2 : 0;                        // chunk-side LDS-DMA: non-temporal when each chunk row has one reader
+    const erh::ErhSeedIo sio /* VAR kPp3Seed: this launch is the sample pass (kernels.h) */,
+    const erh::ErhGroupIo gio /* VAR kPp3Grouped */) {
+    constexpr bool GROUPED = (VAR & kPp3Grouped) != 0;
+    constexpr int kPpAuxX = (VAR & kPp3NtX) ? 2 : 0;                   // chunk-side LDS-DMA: non-temporal when each chunk row has one reader
     const int g_qt = GROUPED ? gio.wg_view[blockIdx.x] : 0;
     const erh::ErhDenseView *const gv = GROUPED ? gio.views + g_qt : nullptr;
-    constexpr bool GSEED = GROUPED && (VAR & 16) != 0;                 // the grouped sample pass: rows [0, seed_rows) of the tile's view
+    constexpr bool GSEED = GROUPED && (VAR & kPp3Seed) != 0;           // the grouped sample pass: rows [0, seed_rows) of the tile's view
     const _Float16 *const X = GROUPED ? gv->X : Xg;
     const int64_t N = GROUPED ? gv->N : Ng;
     const int64_t c0 = GROUPED ? (GSEED ? (int64_t)0 : (int64_t)gv->n0) : c0g;
@@ -721,7 +723,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp3_kernel(
     long long t_mark = (PABL & kPpClocks) ? clock64() : 0;
 #define ERH_PH(I) do { if (PABL & kPpClocks) { const long long n_ = clock64(); tph[I] += n_ - t_mark; t_mark = n_; } } while (0)
     const int nk = d / pp::BK;
-    constexpr bool SEED = (VAR & 16) != 0;                             // sample pass: score the tiles, keep the two best of every cell, no thresholds
+    constexpr bool SEED = (VAR & kPp3Seed) != 0;                       // sample pass: score the tiles, keep the two best of every cell, no thresholds
 
     const int n_qt = Bpad / pp::BN;
     const int64_t n_ct = (c1 - c0 + pp::BM - 1) / pp::BM;
@@ -739,10 +741,10 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp3_kernel(
     const int l31 = lane & 31, hh = lane >> 5;
     const int k0 = ((qt * rot_stages) % nk) & ~1;                      // first K stage of every tile for this query tile
     // Query -> wave mapping: wave column wave_n holds queries wave_n * 32 + l31 (nt = 0) and 128 + wave_n * 32 + l31 (nt = 1) of
-    // the tile, so a batch of at most 128 queries occupies nt = 0 of EVERY wave.  HALFQ (VAR bit 3; batches of 65 ... 128
+    // the tile, so a batch of at most 128 queries occupies nt = 0 of EVERY wave.  HALFQ (VAR kPp3HalfQ; batches of 65 ... 128
     // queries): the nt = 1 half of the tile is not computed at all -- half the MFMAs, no fragment reads and no DMA for query
     // rows 128 ... 255 (8 KiB instead of 16 KiB per query stage) -- same chunk stream, barriers and epilogue.
-    constexpr bool HALFQ = (VAR & 8) != 0;
+    constexpr bool HALFQ = (VAR & kPp3HalfQ) != 0;
     constexpr int NTL = HALFQ ? 1 : 2;
     float t_q[2];
 #pragma unroll
@@ -752,7 +754,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp3_kernel(
     }
     asm volatile("" ::"v"(t_q[0]), "v"(t_q[1]));                      // loaded before the DMA stream starts (keeps vmcnt countable)
 
-    constexpr bool TILED = (VAR & 2) != 0;                             // X is the tiled copy (dense_tile_rows_kernel), c0 % 256 == 0
+    constexpr bool TILED = (VAR & kPp3Tiled) != 0;                     // X is the tiled copy (dense_tile_rows_kernel), c0 % 256 == 0
     const _Float16 *pa[2], *pb[2];
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
@@ -823,7 +825,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp3_kernel(
             --b_left;                                                                                 \
         }                                                                                             \
     } while (0)
-// one instruction (PART 0..3) of the A / B stage pair, then the pair's bookkeeping (VAR bit 0: issued from inside the
+// one instruction (PART 0..3) of the A / B stage pair, then the pair's bookkeeping (VAR kPp3LockStep: issued from inside the
 // matrix segment)
 #define ERH_PP3_PART_A(PART)                                                                          \
     do {                                                                                              \
@@ -916,7 +918,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp3_kernel(
         __builtin_amdgcn_sched_barrier(0);                                                            \
     } while (0)
 // DMA0 / DMA1: which DMA pair (0 none, 1 the A pair, 2 the B pair) is issued, one instruction behind each MFMA pair,
-// inside the first / second K sub-step of the segment (VAR bit 0 only)
+// inside the first / second K sub-step of the segment (VAR kPp3LockStep only)
 #define ERH_PP3_COMPUTE(FIRST, DMA0, DMA1)                                                            \
     do {                                                                                              \
         const char *pa0_ = lds + (a_rd0 + fa_off), *pa1_ = lds + (a_rd1 + fa_off);                    \
@@ -959,7 +961,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp3_kernel(
     } while (0)
     constexpr int kSyncTiles = 4;
 
-// Sample pass (VAR bit 4): of the tile's scores only the two best of every cell -- this lane's 64 rows of one query column --
+// Sample pass (VAR kPp3Seed): of the tile's scores only the two best of every cell -- this lane's 64 rows of one query column --
 // leave the registers.  Three VALU instructions per score, written as inline asm: left to the compiler the chain is
 // re-associated across the 64 accumulators and spills into the main loop.
 #define ERH_PP3_SEED_EPILOGUE()                                                                       \
@@ -1007,7 +1009,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp3_kernel(
     int flush_now = 0;                                                 // workgroup-uniform, decided one tile ahead
     int g = 0;
 
-    if (VAR & 1) {
+    if (VAR & kPp3LockStep) {
         // no memory segments at all: every wave issues the stage's DMA pair from inside its matrix segment (the older
         // group behind the MFMA pairs of the first K sub-step, the younger group behind those of the second, so the two
         // waves of a SIMD block on the memory path at different times) and there is one barrier per stage
@@ -1185,7 +1187,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
     const int total = n_tiles * nk;                                    // flattened (tile, stage) sequence
     const int64_t q_row0 = (int64_t)qt * pp::BN;
     const int64_t lim = (c1 < N) ? c1 : N;
-    const int l31 = lane & 31, hh = lane >> 5;
+    const int l31 = lane & 31;
     const int k0 = (qt * rot_stages) % nk;
     {   // this wave's 64 thresholds -> LDS (loaded and parked before the DMA stream starts: vmcnt stays countable)
         float t_q[2];
@@ -1492,6 +1494,11 @@ static_assert(Cfg2::LDS_BYTES == 160 * 1024, "cfg2");
 static_assert(Cfg0::WAIT_N == 4 && Cfg0::LDS_BYTES == 160 * 1024, "cfg0");
 static_assert(Cfg1::LDS_BYTES == 80 * 1024, "cfg1");
 
+// the 15 leading parameters of every append kernel, from the launchers' argument struct (kernels.h: ErhScanArgs)
+#define ERH_SCAN_ARGS(a)                                                                                   \
+    (a).X, (a).N, (a).d, (a).c0, (a).c1, (a).Q, (a).Bpad, (a).B, (a).tau, (a).filter_dir, (a).dir_id, (a).cand, (a).cand_cnt, (a).cap, \
+        (a).overflow
+
 template <class C>
 hipError_t set_attrs() {
     hipError_t e = hipFuncSetAttribute((const void *)dense_scan_store_kernel<C, false>,
@@ -1527,21 +1534,17 @@ hipError_t set_attrs() {
 #ifdef ERH_MEASURE
 // Persistent launch: `ctas` = workgroups that are co-resident (CUs x workgroups per CU for this configuration).
 template <class C>
-hipError_t launch_persist(const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Q, int Bpad,
-                          int B, const float *tau, const int16_t *filter_dir, const int16_t *dir_id, ErhCand *cand,
-                          uint32_t *cand_cnt, int cap, uint32_t *overflow, int ctas, int pabl, bool ra, hipStream_t st) {
-    const int n_qt = Bpad / C::BN;
+hipError_t launch_persist(const erh::ErhScanArgs &a, int ctas, int pabl, bool ra, hipStream_t st) {
+    const int n_qt = a.Bpad / C::BN;
     int grid_n = ctas / (8 * n_qt) * (8 * n_qt);
     if (grid_n <= 0) return hipErrorInvalidValue;
     dim3 grid((unsigned)grid_n), block(C::NT);
 #define ERH_LAUNCH_P(A)                                                                                    \
     do {                                                                                                   \
         if (ra && C::CAN_RA)                                                                               \
-            hipLaunchKernelGGL((dense_scan_persist_kernel<C, A, C::CAN_RA>), grid, block, C::LDS_BYTES, st, X, N, d, c0, \
-                               c1, Q, Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow);     \
+            hipLaunchKernelGGL((dense_scan_persist_kernel<C, A, C::CAN_RA>), grid, block, C::LDS_BYTES, st, ERH_SCAN_ARGS(a)); \
         else                                                                                               \
-            hipLaunchKernelGGL((dense_scan_persist_kernel<C, A, false>), grid, block, C::LDS_BYTES, st, X, N, d, c0, c1, \
-                               Q, Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow);         \
+            hipLaunchKernelGGL((dense_scan_persist_kernel<C, A, false>), grid, block, C::LDS_BYTES, st, ERH_SCAN_ARGS(a)); \
     } while (0)
     if constexpr (C::MEASURE) {
         switch (pabl) {
@@ -1583,17 +1586,12 @@ hipError_t launch_store_grouped(const erh::ErhDenseView *views, int n0_max, cons
 }
 
 template <class C>
-hipError_t launch_append(const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Q, int Bpad,
-                         int B, const float *tau, const int16_t *filter_dir, const int16_t *dir_id, ErhCand *cand,
-                         uint32_t *cand_cnt, int cap, uint32_t *overflow, int ablate, unsigned long long *dbg,
-                         hipStream_t st) {
-    const int n_qt = Bpad / C::BN;
-    const int64_t n_ct = (c1 - c0 + C::BM - 1) / C::BM;
+hipError_t launch_append(const erh::ErhScanArgs &a, int ablate, unsigned long long *dbg, hipStream_t st) {
+    const int n_qt = a.Bpad / C::BN;
+    const int64_t n_ct = (a.c1 - a.c0 + C::BM - 1) / C::BM;
     const int64_t n_ct8 = (n_ct + 7) / 8 * 8;
     dim3 grid((unsigned)(n_ct8 * n_qt)), block(C::NT);
-#define ERH_LAUNCH_ABL(A)                                                                                  \
-    hipLaunchKernelGGL((dense_scan_append_kernel<C, A>), grid, block, C::LDS_BYTES, st, X, N, d, c0, c1, Q, Bpad, B, \
-                       tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, dbg)
+#define ERH_LAUNCH_ABL(A) hipLaunchKernelGGL((dense_scan_append_kernel<C, A>), grid, block, C::LDS_BYTES, st, ERH_SCAN_ARGS(a), dbg)
     if constexpr (C::MEASURE) {
         switch (ablate) {
             case 1: ERH_LAUNCH_ABL(1); break;
@@ -1632,105 +1630,112 @@ constexpr int pp_mask_of(int code) {
         default: return 0;
     }
 }
-#define ERH_PP_MASKS(X) X(1) X(2) X(5) X(25) X(9) X(33) X(17) X(37) X(29) X(61) X(65) X(64) X(89) X(57) X(121)
+// the masks that are instantiated, as X(mask, V) for a V of the caller's
+#define ERH_PP_MASKS(X, V)                                                                                 \
+    X(1, V) X(2, V) X(5, V) X(25, V) X(9, V) X(33, V) X(17, V) X(37, V) X(29, V) X(61, V) X(65, V) X(64, V) X(89, V) X(57, V) X(121, V)
 #endif
 
-// the half-query-tile mode (VAR bit 3) is instantiated for the full kernel and, in measurement builds, for "no epilogue"
-constexpr bool pp3_halfq_ok(int mask) { return mask == 0 || mask == 1; }
-constexpr int pp3_halfq_mask(int mask) { return pp3_halfq_ok(mask) ? mask : 0; }
+// ---- dense_scan_pp3_kernel<PABL, VAR>: the one list of instantiations.  dense_scan_init sets the LDS attribute of every entry and
+// launch_pp3_variant launches by (PABL, VAR) from the same list, so an instantiation cannot be launched without its attribute.
+#define ERH_PP3_PRODUCT(X)                                                                                 \
+    X(0, 0) X(0, 2) X(0, 8) X(0, 10)                   /* row-major / tiled chunk operand, whole / half query tile */ \
+    X(0, 16) X(0, 24)                                  /* the sample pass */                               \
+    X(0, 32) X(0, 40) X(0, 48) X(0, 56)                /* the grouped launch and its sample pass */        \
+    X(0, 64) X(0, 72) X(0, 96) X(0, 104)               /* chunk-side loads with the non-temporal hint, ordinary and grouped */
+#ifdef ERH_MEASURE   // ... + the lock-step variant, "no epilogue" on the half tile, every ablation mask on the whole tile
+#define ERH_PP3_VARIANTS(X)                                                                                \
+    ERH_PP3_PRODUCT(X) X(0, 1) X(1, 8) X(1, 10) ERH_PP_MASKS(X, 0) ERH_PP_MASKS(X, 1) ERH_PP_MASKS(X, 2)
+// the lean kernel (dense_scan_pp2_kernel<PABL, VAR>): every mask, and its VAR 1 ... 3 without and with "no epilogue" / phase clocks
+#define ERH_PP2_VARIANTS(X)                                                                                \
+    X(0, 0) ERH_PP_MASKS(X, 0) X(0, 1) X(0, 2) X(0, 3) X(1, 1) X(1, 2) X(1, 3) X(64, 1) X(64, 2) X(64, 3) X(65, 1) X(65, 2) X(65, 3)
+#else
+#define ERH_PP3_VARIANTS(X) ERH_PP3_PRODUCT(X)
+#endif
 
-hipError_t launch_pp(const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Q, int Bpad, int B,
-                     const float *tau, const int16_t *filter_dir, const int16_t *dir_id, ErhCand *cand,
-                     uint32_t *cand_cnt, int cap, uint32_t *overflow, int ctas, int pabl, unsigned long long *dbg,
-                     int lean, uint32_t *stream_sync, const erh::ErhSeedIo *sio, hipStream_t st) {
-    const int n_qt = Bpad / pp::BN;
+// (tiled, halfq, seed, grouped, nt) -> VAR.  The sample pass reads row-major operands; the nt hint is for the row-major whole-stream scan.
+constexpr int pp3_variant(bool tiled, bool halfq, bool seed, bool grouped, bool nt) {
+    const int hq = halfq ? kPp3HalfQ : 0;
+    if (grouped) return kPp3Grouped | (seed ? kPp3Seed : 0) | (nt && !seed ? kPp3NtX : 0) | hq;
+    if (seed) return kPp3Seed | hq;
+    if (nt) return kPp3NtX | hq;
+    return hq | (tiled ? kPp3Tiled : 0);
+}
+static_assert(pp3_variant(0, 0, 0, 0, 0) == 0 && pp3_variant(1, 0, 0, 0, 0) == 2 && pp3_variant(0, 1, 0, 0, 0) == 8 &&
+              pp3_variant(1, 1, 0, 0, 0) == 10, "pp3: plain");
+static_assert(pp3_variant(0, 0, 1, 0, 0) == 16 && pp3_variant(1, 0, 1, 0, 1) == 16 && pp3_variant(0, 1, 1, 0, 0) == 24 &&
+              pp3_variant(1, 1, 1, 0, 1) == 24, "pp3: sample pass");
+static_assert(pp3_variant(0, 0, 0, 0, 1) == 64 && pp3_variant(1, 0, 0, 0, 1) == 64 && pp3_variant(0, 1, 0, 0, 1) == 72, "pp3: nt");
+static_assert(pp3_variant(0, 0, 0, 1, 0) == 32 && pp3_variant(0, 1, 0, 1, 0) == 40 && pp3_variant(0, 0, 1, 1, 0) == 48 &&
+              pp3_variant(0, 1, 1, 1, 0) == 56 && pp3_variant(0, 0, 1, 1, 1) == 48 && pp3_variant(0, 1, 1, 1, 1) == 56 &&
+              pp3_variant(0, 0, 0, 1, 1) == 96 && pp3_variant(0, 1, 0, 1, 1) == 104, "pp3: grouped");
+
+constexpr int pp_key(int pabl, int var) { return pabl << 8 | var; }
+
+// hipErrorInvalidValue: (pabl, var) is not in the list
+hipError_t launch_pp3_variant(int pabl, int var, dim3 grid, const erh::ErhScanArgs &a, unsigned long long *dbg, int rot,
+                              uint32_t *stream_sync, const erh::ErhSeedIo &sio, const erh::ErhGroupIo &gio, hipStream_t st) {
+    switch (pp_key(pabl, var)) {
+#define ERH_PP3_CASE(A, V)                                                                                 \
+    case pp_key(A, V):                                                                                     \
+        hipLaunchKernelGGL((dense_scan_pp3_kernel<A, V>), grid, dim3(pp::NT), pp::LDS_BYTES, st, ERH_SCAN_ARGS(a), dbg, rot, stream_sync, \
+                           sio, gio);                                                                      \
+        return hipGetLastError();
+        ERH_PP3_VARIANTS(ERH_PP3_CASE)
+#undef ERH_PP3_CASE
+        default: return hipErrorInvalidValue;
+    }
+}
+
+#ifdef ERH_MEASURE
+hipError_t launch_pp2_variant(int pabl, int var, dim3 grid, const erh::ErhScanArgs &a, unsigned long long *dbg, int rot, hipStream_t st) {
+    switch (pp_key(pabl, var)) {
+#define ERH_PP2_CASE(A, V)                                                                                 \
+    case pp_key(A, V):                                                                                     \
+        hipLaunchKernelGGL((dense_scan_pp2_kernel<A, V>), grid, dim3(pp::NT), pp::LDS_BYTES, st, ERH_SCAN_ARGS(a), dbg, rot); \
+        return hipGetLastError();
+        ERH_PP2_VARIANTS(ERH_PP2_CASE)
+#undef ERH_PP2_CASE
+        default: return hipErrorInvalidValue;
+    }
+}
+#endif
+
+hipError_t launch_pp(const erh::ErhScanArgs &a, int ctas, int pabl, unsigned long long *dbg, const erh::ErhPpMode &mode,
+                     uint32_t *stream_sync, const erh::ErhSeedIo *sio, hipStream_t st) {
+    const int n_qt = a.Bpad / pp::BN;
     const int grid_n = ctas / (8 * n_qt) * (8 * n_qt);
     if (grid_n <= 0) return hipErrorInvalidValue;
     erh::ErhSeedIo sio_v{};
     if (sio) sio_v = *sio;
     const bool seed = sio_v.mode == 1;
-    if (sio_v.mode != 0 && !(lean & 8)) return hipErrorInvalidValue;    // the sample pass exists for the strict ping-pong kernel only
-    const int64_t n_ct = (c1 - c0 + pp::BM - 1) / pp::BM;
+    if (sio_v.mode != 0 && !mode.strict) return hipErrorInvalidValue;    // the sample pass exists for the strict ping-pong kernel only
+    const int64_t n_ct = (a.c1 - a.c0 + pp::BM - 1) / pp::BM;
     if (n_ct / (grid_n / n_qt) + 1 >= (1ll << pp::TILE_BITS)) return hipErrorInvalidValue;   // tile index must fit the record
-    dim3 grid((unsigned)grid_n), block(pp::NT);
-    // lean: bit 0 = lean-issue kernel, bits 1-2 = its VAR, bits 8.. = rot_stages (see dense_scan_pp2_kernel)
-    const int var = (lean >> 1) & 3, rot = lean >> 8;
-    const bool halfq = (lean & 8) && B <= pp::BN / 2 && Bpad == pp::BN;
-    // lean bit 4: chunk-side LDS-DMA with the non-temporal hint -- only where every chunk row has ONE reader (one query tile), on the
-    // row-major plain variant of the strict ping-pong kernel
-    const bool nt_x = (lean & 16) && (lean & 8) && n_qt == 1 && var == 0 && !seed && pabl == 0;
-#define ERH_LAUNCH_PP2(A, V)                                                                               \
-    hipLaunchKernelGGL((dense_scan_pp2_kernel<A, V>), grid, block, pp::LDS_BYTES, st, X, N, d, c0, c1, Q, Bpad, B, \
-                       tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, dbg, rot)
-#define ERH_LAUNCH_PP3V(A, V)                                                                              \
-    hipLaunchKernelGGL((dense_scan_pp3_kernel<A, V>), grid, block, pp::LDS_BYTES, st, X, N, d, c0, c1, Q, Bpad, B, tau, \
-                       filter_dir, dir_id, cand, cand_cnt, cap, overflow, dbg, rot, stream_sync, sio_v, erh::ErhGroupIo{})
-#define ERH_LAUNCH_PP3(A)                                                                                  \
-    do {                                                                                                   \
-        if (seed) {                                        /* the sample pass: row-major operands, full kernel only */ \
-            if (halfq) ERH_LAUNCH_PP3V(0, 24); else ERH_LAUNCH_PP3V(0, 16);                                \
-        } else if (nt_x) {                                                                                 \
-            if (halfq) ERH_LAUNCH_PP3V(0, 72); else ERH_LAUNCH_PP3V(0, 64);                                \
-        } else if (halfq && pp3_halfq_ok(A)) {             /* 65 ... 128 queries: the nt = 1 half of the tile is not computed */ \
-            if (var & 2) ERH_LAUNCH_PP3V(pp3_halfq_mask(A), 10); else ERH_LAUNCH_PP3V(pp3_halfq_mask(A), 8); \
-        } else if (var & 2)                                                                                \
-            hipLaunchKernelGGL((dense_scan_pp3_kernel<A, 2>), grid, block, pp::LDS_BYTES, st, X, N, d, c0, c1, Q, Bpad, \
-                               B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, dbg, rot, stream_sync, sio_v, erh::ErhGroupIo{}); \
-        else if ((var & 1) && kPp3LockStep)                                                                \
-            hipLaunchKernelGGL((dense_scan_pp3_kernel<A, kPp3LockStep>), grid, block, pp::LDS_BYTES, st, X, N, d, c0, c1, Q, \
-                               Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, dbg, rot, stream_sync, sio_v, erh::ErhGroupIo{}); \
-        else                                                                                               \
-            hipLaunchKernelGGL((dense_scan_pp3_kernel<A, 0>), grid, block, pp::LDS_BYTES, st, X, N, d, c0, c1, Q, Bpad, \
-                               B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, dbg, rot, stream_sync, sio_v, erh::ErhGroupIo{}); \
-    } while (0)
+    const dim3 grid((unsigned)grid_n);
 #ifdef ERH_MEASURE
-#define ERH_LAUNCH_PP(A)                                                                                   \
-    do {                                                                                                   \
-        if (lean & 8)                                                                                      \
-            ERH_LAUNCH_PP3(A);                                                                             \
-        else if (lean & 1)                                                                                 \
-            ERH_LAUNCH_PP2(A, 0);                                                                          \
-        else                                                                                               \
-            hipLaunchKernelGGL((dense_scan_pp_kernel<0>), grid, block, pp::LDS_BYTES, st, X, N, d, c0, c1, Q, Bpad, B, \
-                               tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, dbg);                \
-    } while (0)
-#endif
-#define ERH_LAUNCH_PP2V(A)                                                                                 \
-    do {                                                                                                   \
-        switch (var) {                                                                                     \
-            case 1: ERH_LAUNCH_PP2(A, 1); break;                                                           \
-            case 2: ERH_LAUNCH_PP2(A, 2); break;                                                           \
-            case 3: ERH_LAUNCH_PP2(A, 3); break;                                                           \
-            default: ERH_LAUNCH_PP2(A, 0); break;                                                          \
-        }                                                                                                  \
-    } while (0)
-#ifdef ERH_MEASURE
-    const int mask = pp_mask_of(pabl);
-    if ((lean & 1) && !(lean & 8) && var != 0 && (mask == 0 || mask == 1 || mask == 64 || mask == 65)) {
-        switch (mask) {
-            case 1: ERH_LAUNCH_PP2V(1); break;
-            case 64: ERH_LAUNCH_PP2V(64); break;
-            case 65: ERH_LAUNCH_PP2V(65); break;
-            default: ERH_LAUNCH_PP2V(0); break;
-        }
+    int mask = pp_mask_of(pabl);
+    if (!mode.strict) {                     // the first two generations; the lean kernel has its VAR 1 ... 3 for four of the masks only
+        if (mode.lean)
+            return launch_pp2_variant(mask, (mask == 0 || mask == 1 || mask == 64 || mask == 65) ? mode.var : 0, grid, a, dbg,
+                                      mode.rot_stages, st);
+        hipLaunchKernelGGL((dense_scan_pp_kernel<0>), grid, dim3(pp::NT), pp::LDS_BYTES, st, ERH_SCAN_ARGS(a), dbg);
         return hipGetLastError();
     }
-    switch (mask) {
-#define ERH_PP_CASE(M) case M: ERH_LAUNCH_PP(M); break;
-        ERH_PP_MASKS(ERH_PP_CASE)
-#undef ERH_PP_CASE
-        default: ERH_LAUNCH_PP(0); break;
-    }
 #else
-    (void)pabl;
-    ERH_LAUNCH_PP3(0);                      // the product build carries the strict ping-pong kernel only (dense_pp 1 ... 3)
+    int mask = 0;                           // the product build carries the strict ping-pong kernel only (dense_pp 1 ... 3)
 #endif
-#undef ERH_LAUNCH_PP2V
-#undef ERH_LAUNCH_PP2
-#undef ERH_LAUNCH_PP3
-#undef ERH_LAUNCH_PP3V
-#undef ERH_LAUNCH_PP
-    return hipGetLastError();
+    // the half query tile: 65 ... 128 queries, the nt = 1 half of the tile is not computed
+    bool halfq = mode.strict && a.B <= pp::BN / 2 && a.Bpad == pp::BN;
+    // chunk-side LDS-DMA with the non-temporal hint -- only where every chunk row has ONE reader (one query tile), on the row-major plain
+    // variant of the strict ping-pong kernel
+    const bool nt_x = mode.nt && mode.strict && n_qt == 1 && mode.var == 0 && !seed && pabl == 0;
+    if (seed || nt_x) mask = 0;             // full kernel only
+    if (mask > 1) halfq = false;            // the half tile is instantiated for the full kernel and, in measurement builds, for "no epilogue"
+    int var = pp3_variant((mode.var & 2) != 0, halfq, seed, false, nt_x);
+#ifdef ERH_MEASURE
+    if (var == 0 && (mode.var & 1)) var = kPp3LockStep;
+#endif
+    return launch_pp3_variant(mask, var, grid, a, dbg, mode.rot_stages, stream_sync, sio_v, erh::ErhGroupIo{}, st);
 }
 
 }  // namespace
@@ -1747,57 +1752,33 @@ hipError_t dense_scan_init() {
     if (e != hipSuccess) return e;
     e = set_attrs<Cfg2>();
     if (e != hipSuccess) return e;
-#define ERH_SET_PP3(A, V)                                                                                  \
-    e = hipFuncSetAttribute((const void *)dense_scan_pp3_kernel<A, V>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            pp::LDS_BYTES);                                                                \
+#define ERH_SET_LDS(K)                                                                                     \
+    e = hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, pp::LDS_BYTES);   \
     if (e != hipSuccess) return e;
-#define ERH_SET_PP(A) ERH_SET_PP3(A, 0) ERH_SET_PP3(A, 2)
-    ERH_SET_PP(0)
-    ERH_SET_PP3(0, 8) ERH_SET_PP3(0, 10) ERH_SET_PP3(0, 16) ERH_SET_PP3(0, 24)
-    ERH_SET_PP3(0, 32) ERH_SET_PP3(0, 40)              // the grouped launch (several matrices, one per query tile), whole / half query tile
-    ERH_SET_PP3(0, 48) ERH_SET_PP3(0, 56)              // ... and its sample pass
-    ERH_SET_PP3(0, 64) ERH_SET_PP3(0, 72) ERH_SET_PP3(0, 96) ERH_SET_PP3(0, 104)   // chunk-side loads with the non-temporal hint (one query tile per matrix)
-    e = hipFuncSetAttribute((const void *)dense_scan_pp5_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, pp::LDS_BYTES);
-    if (e != hipSuccess) return e;
+#define ERH_SET_PP3(A, V) ERH_SET_LDS((dense_scan_pp3_kernel<A, V>))
+    ERH_PP3_VARIANTS(ERH_SET_PP3)
+#undef ERH_SET_PP3
+    ERH_SET_LDS(dense_scan_pp5_kernel)
 #ifdef ERH_MEASURE
-    e = hipFuncSetAttribute((const void *)dense_scan_pp_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            pp::LDS_BYTES);
-    if (e != hipSuccess) return e;
-#define ERH_SET_PP2V(A, V)                                                                                 \
-    e = hipFuncSetAttribute((const void *)dense_scan_pp2_kernel<A, V>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            pp::LDS_BYTES);                                                                \
-    if (e != hipSuccess) return e;
-#define ERH_SET_PP4(A)                                                                                     \
-    e = hipFuncSetAttribute((const void *)dense_scan_pp4_kernel<A>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                            pp::LDS_BYTES);                                                                \
-    if (e != hipSuccess) return e;
-#define ERH_SET_MEASURE(A) ERH_SET_PP(A) ERH_SET_PP3(A, 1) ERH_SET_PP2V(A, 0) ERH_SET_PP4(A)
-    ERH_SET_PP3(0, 1) ERH_SET_PP2V(0, 0) ERH_SET_PP4(0) ERH_SET_PP3(1, 8) ERH_SET_PP3(1, 10)
-    ERH_PP_MASKS(ERH_SET_MEASURE)
-    ERH_SET_PP2V(0, 1) ERH_SET_PP2V(0, 2) ERH_SET_PP2V(0, 3)
-    ERH_SET_PP2V(1, 1) ERH_SET_PP2V(1, 2) ERH_SET_PP2V(1, 3)
-    ERH_SET_PP2V(64, 1) ERH_SET_PP2V(64, 2) ERH_SET_PP2V(64, 3)
-    ERH_SET_PP2V(65, 1) ERH_SET_PP2V(65, 2) ERH_SET_PP2V(65, 3)
-#undef ERH_SET_MEASURE
-#undef ERH_SET_PP2V
+    ERH_SET_LDS(dense_scan_pp_kernel<0>)
+#define ERH_SET_PP2(A, V) ERH_SET_LDS((dense_scan_pp2_kernel<A, V>))
+    ERH_PP2_VARIANTS(ERH_SET_PP2)
+#undef ERH_SET_PP2
+#define ERH_SET_PP4(A, V) ERH_SET_LDS(dense_scan_pp4_kernel<A>)
+    ERH_SET_PP4(0, 0) ERH_PP_MASKS(ERH_SET_PP4, 0)
 #undef ERH_SET_PP4
 #endif
-#undef ERH_SET_PP
-#undef ERH_SET_PP3
+#undef ERH_SET_LDS
     return hipSuccess;
 }
 
 // Ping-pong persistent append scan; hipErrorInvalidValue when the shape does not qualify (fewer than 8 stages of
 // 32 halves, query tiles that do not divide the resident grid, tile index too wide for the record).
-hipError_t launch_dense_scan_pp(const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Q,
-                                int Bpad, int B, const float *tau, const int16_t *filter_dir, const int16_t *dir_id,
-                                ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus, int pabl,
-                                unsigned long long *dbg, int lean, uint32_t *stream_sync, const ErhSeedIo *sio,
-                                hipStream_t st) {
-    if (c1 <= c0) return hipSuccess;
-    if (d % (2 * pp::BK) != 0 || d / pp::BK < 8) return hipErrorInvalidValue;   // stage pairs never straddle a tile
-    return launch_pp(X, N, d, c0, c1, Q, Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, n_cus, pabl,
-                     dbg, lean, stream_sync, sio, st);
+hipError_t launch_dense_scan_pp(const ErhScanArgs &a, int n_cus, int pabl, unsigned long long *dbg, const ErhPpMode &mode,
+                                uint32_t *stream_sync, const ErhSeedIo *sio, hipStream_t st) {
+    if (a.c1 <= a.c0) return hipSuccess;
+    if (a.d % (2 * pp::BK) != 0 || a.d / pp::BK < 8) return hipErrorInvalidValue;   // stage pairs never straddle a tile
+    return launch_pp(a, n_cus, pabl, dbg, mode, stream_sync, sio, st);
 }
 
 // The grouped launches (kernels.h: ErhDenseView / ErhGroupIo).  Store: every query tile against the seed prefix of its own matrix;
@@ -1816,16 +1797,10 @@ hipError_t launch_dense_scan_pp_grouped(const ErhGroupIo &gio, int grid, int d, 
     if (d % (2 * pp::BK) != 0 || d / pp::BK < 8) return hipErrorInvalidValue;
     erh::ErhSeedIo sio_v{};
     if (sio) sio_v = *sio;
-#define ERH_LAUNCH_PP3G(V)                                                                                 \
-    hipLaunchKernelGGL((dense_scan_pp3_kernel<0, V>), dim3((unsigned)grid), dim3(pp::NT), pp::LDS_BYTES, st, (const _Float16 *)nullptr, \
-                       (int64_t)0, d, (int64_t)0, (int64_t)0, Q, Bpad, Bpad, tau, (const int16_t *)nullptr, (const int16_t *)nullptr, cand, \
-                       cand_cnt, cap, overflow, (unsigned long long *)nullptr, 0, (uint32_t *)nullptr, sio_v, gio)
-    if (sio_v.mode == 1) { if (halfq) ERH_LAUNCH_PP3G(56); else ERH_LAUNCH_PP3G(48); }
-    else if (nt) { if (halfq) ERH_LAUNCH_PP3G(104); else ERH_LAUNCH_PP3G(96); }
-    else if (halfq) ERH_LAUNCH_PP3G(40);
-    else ERH_LAUNCH_PP3G(32);
-#undef ERH_LAUNCH_PP3G
-    return hipGetLastError();
+    ErhScanArgs a{};                        // the views replace (X, N, c0, c1); padding rows carry tau = +inf, so B = Bpad; no dir filter
+    a.d = d; a.Q = Q; a.Bpad = a.B = Bpad; a.tau = tau; a.cand = cand; a.cand_cnt = cand_cnt; a.cap = cap; a.overflow = overflow;
+    return launch_pp3_variant(0, pp3_variant(false, halfq != 0, sio_v.mode == 1, true, nt != 0), dim3((unsigned)grid), a, nullptr, 0, nullptr,
+                              sio_v, gio, st);
 }
 
 int dense_scan_pp_streams(int n_cus, int Bpad) {
@@ -1835,36 +1810,29 @@ int dense_scan_pp_streams(int n_cus, int Bpad) {
     return grid_n > 0 ? (grid_n / (8 * n_qt)) * 8 : 0;
 }
 
-// The tiled-operand ping-pong scan (dense_scan_pp4_kernel): Xt / Qt are the tiled copies (launch_dense_tile_rows) of the
+#ifdef ERH_MEASURE
+// The tiled-operand ping-pong scan (dense_scan_pp4_kernel): a.X / a.Q are the tiled copies (launch_dense_tile_rows) of the
 // chunk matrix and of the query block; c0 must be a multiple of 256.  hipErrorInvalidValue when the shape does not qualify.
-hipError_t launch_dense_scan_pp4(const _Float16 *Xt, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Qt,
-                                 int Bpad, int B, const float *tau, const int16_t *filter_dir, const int16_t *dir_id,
-                                 ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus, int pabl,
-                                 unsigned long long *dbg, int rot_stages, hipStream_t st) {
-#ifndef ERH_MEASURE
-    return hipErrorInvalidValue;            // measurement builds only: the caller falls through to the strict ping-pong scan
-#else
-    if (c1 <= c0) return hipSuccess;
-    if (d % pp::BK != 0 || d / pp::BK < 8 || c0 % pp::BM != 0) return hipErrorInvalidValue;
-    const int n_qt = Bpad / pp::BN;
+hipError_t launch_dense_scan_pp4(const ErhScanArgs &a, int n_cus, int pabl, unsigned long long *dbg, int rot_stages, hipStream_t st) {
+    if (a.c1 <= a.c0) return hipSuccess;
+    if (a.d % pp::BK != 0 || a.d / pp::BK < 8 || a.c0 % pp::BM != 0) return hipErrorInvalidValue;
+    const int n_qt = a.Bpad / pp::BN;
     const int grid_n = n_cus / (8 * n_qt) * (8 * n_qt);
     if (grid_n <= 0) return hipErrorInvalidValue;
-    const int64_t n_ct = (c1 - c0 + pp::BM - 1) / pp::BM;
+    const int64_t n_ct = (a.c1 - a.c0 + pp::BM - 1) / pp::BM;
     if (n_ct / (grid_n / n_qt) + 1 >= (1ll << pp::TILE_BITS)) return hipErrorInvalidValue;   // tile index must fit the record
     dim3 grid((unsigned)grid_n), block(pp::NT);
-#define ERH_LAUNCH_PP4(A)                                                                                  \
-    hipLaunchKernelGGL((dense_scan_pp4_kernel<A>), grid, block, pp::LDS_BYTES, st, Xt, N, d, c0, c1, Qt, Bpad, B, tau, \
-                       filter_dir, dir_id, cand, cand_cnt, cap, overflow, dbg, rot_stages)
+#define ERH_LAUNCH_PP4(A) hipLaunchKernelGGL((dense_scan_pp4_kernel<A>), grid, block, pp::LDS_BYTES, st, ERH_SCAN_ARGS(a), dbg, rot_stages)
     switch (pp_mask_of(pabl)) {
-#define ERH_PP_CASE(M) case M: ERH_LAUNCH_PP4(M); break;
-        ERH_PP_MASKS(ERH_PP_CASE)
+#define ERH_PP_CASE(M, V) case M: ERH_LAUNCH_PP4(M); break;
+        ERH_PP_MASKS(ERH_PP_CASE, 0)
 #undef ERH_PP_CASE
         default: ERH_LAUNCH_PP4(0); break;
     }
 #undef ERH_LAUNCH_PP4
     return hipGetLastError();
-#endif
 }
+#endif
 
 hipError_t launch_dense_tile_rows(const _Float16 *X, int64_t N, int d, void *Xt, hipStream_t st) {
     if (d % 64 != 0) return hipErrorInvalidValue;
@@ -1886,21 +1854,17 @@ hipError_t launch_dense_tile_rows_n(const _Float16 *X, int64_t N, int d, int row
     return hipGetLastError();
 }
 
-// The 384 x 256 ping-pong scan (dense_scan_pp5_kernel): Xt = launch_dense_tile_rows_n(X, N, d, 384), Qt = launch_dense_tile_rows of the
+// The 384 x 256 ping-pong scan (dense_scan_pp5_kernel): a.X = launch_dense_tile_rows_n(X, N, d, 384), a.Q = launch_dense_tile_rows of the
 // query block; c0 must be a multiple of 384, Bpad >= 512.  hipErrorInvalidValue when the shape does not qualify.
-hipError_t launch_dense_scan_pp5(const _Float16 *Xt, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Qt,
-                                 int Bpad, int B, const float *tau, const int16_t *filter_dir, const int16_t *dir_id,
-                                 ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus, int rot_stages,
-                                 hipStream_t st) {
-    if (c1 <= c0) return hipSuccess;
-    if (d % 64 != 0 || d / pp::BK < 8 || c0 % pp5::BM != 0 || Bpad % pp::BN != 0 || Bpad < 2 * pp::BN) return hipErrorInvalidValue;
-    const int n_qt = Bpad / pp::BN;
+hipError_t launch_dense_scan_pp5(const ErhScanArgs &a, int n_cus, int rot_stages, hipStream_t st) {
+    if (a.c1 <= a.c0) return hipSuccess;
+    if (a.d % 64 != 0 || a.d / pp::BK < 8 || a.c0 % pp5::BM != 0 || a.Bpad % pp::BN != 0 || a.Bpad < 2 * pp::BN) return hipErrorInvalidValue;
+    const int n_qt = a.Bpad / pp::BN;
     const int grid_n = n_cus / (8 * n_qt) * (8 * n_qt);
     if (grid_n <= 0) return hipErrorInvalidValue;
-    const int64_t n_ct = (c1 - c0 + pp5::BM - 1) / pp5::BM;
+    const int64_t n_ct = (a.c1 - a.c0 + pp5::BM - 1) / pp5::BM;
     if (n_ct / (grid_n / n_qt) + 1 >= (1ll << pp5::TILE_BITS)) return hipErrorInvalidValue;   // tile index must fit the record
-    hipLaunchKernelGGL(dense_scan_pp5_kernel, dim3((unsigned)grid_n), dim3(pp::NT), pp::LDS_BYTES, st, Xt, N, d, c0, c1, Qt,
-                       Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, rot_stages);
+    hipLaunchKernelGGL(dense_scan_pp5_kernel, dim3((unsigned)grid_n), dim3(pp::NT), pp::LDS_BYTES, st, ERH_SCAN_ARGS(a), rot_stages);
     return hipGetLastError();
 }
 
@@ -1912,44 +1876,27 @@ hipError_t launch_dense_scan_store(int cfg, const _Float16 *Q, int Bpad, const _
     return launch_store<Cfg0>(Q, Bpad, X, N, d, c0, nc, S0, ld_s0, st);
 }
 
-hipError_t launch_dense_scan_append(int cfg, const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1,
-                                    const _Float16 *Q, int Bpad, int B, const float *tau,
-                                    const int16_t *filter_dir, const int16_t *dir_id,
-                                    ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int ablate,
-                                    unsigned long long *dbg, hipStream_t st) {
-    if (c1 <= c0) return hipSuccess;
-    if (cfg == 1)
-        return launch_append<Cfg1>(X, N, d, c0, c1, Q, Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow,
-                                   ablate, dbg, st);
-    if (cfg == 2)
-        return launch_append<Cfg2>(X, N, d, c0, c1, Q, Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow,
-                                   ablate, dbg, st);
-    return launch_append<Cfg0>(X, N, d, c0, c1, Q, Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow,
-                               ablate, dbg, st);
+hipError_t launch_dense_scan_append(int cfg, const ErhScanArgs &a, int ablate, unsigned long long *dbg, hipStream_t st) {
+    if (a.c1 <= a.c0) return hipSuccess;
+    if (cfg == 1) return launch_append<Cfg1>(a, ablate, dbg, st);
+    if (cfg == 2) return launch_append<Cfg2>(a, ablate, dbg, st);
+    return launch_append<Cfg0>(a, ablate, dbg, st);
 }
 
+#ifdef ERH_MEASURE
 // Persistent variant of the append scan; returns hipErrorInvalidValue when the shape does not qualify
 // (query tiles do not divide the resident grid, or too few K-steps) so that the caller uses the plain launch.
-hipError_t launch_dense_scan_persist(int cfg, const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1,
-                                     const _Float16 *Q, int Bpad, int B, const float *tau,
-                                     const int16_t *filter_dir, const int16_t *dir_id,
-                                     ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus,
-                                     int pabl, int readahead, hipStream_t st) {
-#ifndef ERH_MEASURE
-    return hipErrorInvalidValue;                 // the lock-step persistent kernel exists in measurement builds only
-#else
-    if (c1 <= c0) return hipSuccess;
+hipError_t launch_dense_scan_persist(int cfg, const ErhScanArgs &a, int n_cus, int pabl, int readahead, hipStream_t st) {
+    if (a.c1 <= a.c0) return hipSuccess;
     if (cfg == 1) return hipErrorInvalidValue;   // the two-workgroup configuration keeps the per-tile launch
     if (cfg == 2) {
-        if (d / Cfg2::BK <= Cfg2::DA) return hipErrorInvalidValue;
-        return launch_persist<Cfg2>(X, N, d, c0, c1, Q, Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow,
-                                    n_cus, pabl, readahead != 0, st);
+        if (a.d / Cfg2::BK <= Cfg2::DA) return hipErrorInvalidValue;
+        return launch_persist<Cfg2>(a, n_cus, pabl, readahead != 0, st);
     }
-    if (d / Cfg0::BK <= Cfg0::DA) return hipErrorInvalidValue;
-    return launch_persist<Cfg0>(X, N, d, c0, c1, Q, Bpad, B, tau, filter_dir, dir_id, cand, cand_cnt, cap, overflow, n_cus,
-                                pabl, false, st);
-#endif
+    if (a.d / Cfg0::BK <= Cfg0::DA) return hipErrorInvalidValue;
+    return launch_persist<Cfg0>(a, n_cus, pabl, false, st);
 }
+#endif
 
 hipError_t launch_dense_naive(const _Float16 *Q, int B, const _Float16 *X, int64_t row0, int rows, int d,
                               float *out, hipStream_t st) {

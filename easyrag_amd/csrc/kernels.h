@@ -69,49 +69,56 @@ int dense_scan_pp_streams(int n_cus, int Bpad);
 hipError_t dense_scan_init();
 hipError_t launch_dense_scan_store(int cfg, const _Float16 *Q, int Bpad, const _Float16 *X, int64_t N, int d,
                                    int64_t c0, int nc, float *S0, int ld_s0, hipStream_t st);
-hipError_t launch_dense_scan_append(int cfg, const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1,
-                                    const _Float16 *Q, int Bpad, int B, const float *tau,
-                                    const int16_t *filter_dir, const int16_t *dir_id,
-                                    ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int ablate,
-                                    unsigned long long *dbg, hipStream_t st);
-hipError_t launch_dense_scan_pp(const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Q,
-                                int Bpad, int B, const float *tau, const int16_t *filter_dir, const int16_t *dir_id,
-                                ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus, int pabl,
-                                unsigned long long *dbg, int lean /* the lean-issue kernel: X must be padded by kDensePadRows zero rows */,
+// What every launcher of the append stage takes: rows [c0, c1) of the chunk matrix against the query block, thresholds in, candidates out.
+// A caller fills it once; the launchers unpack it where the kernel is launched (kernel parameter lists are positional).
+struct ErhScanArgs {
+    const _Float16 *X;                        // chunk matrix [N x d] (row-major, or the tiled copy the launcher names)
+    int64_t N;
+    int d;
+    int64_t c0, c1;
+    const _Float16 *Q;                        // query block [Bpad x d] (or its tiled copy), the first B rows are queries
+    int Bpad, B;
+    const float *tau;                         // [B] pruning thresholds
+    const int16_t *filter_dir, *dir_id;       // [B] dir filter and [N] dir of every stored row, or null
+    ErhCand *cand;                            // [B][cap] candidates, cand_cnt[B] their counts
+    uint32_t *cand_cnt;
+    int cap;
+    uint32_t *overflow;                       // flag word: a list ran over
+};
+// Which ping-pong kernel launch_dense_scan_pp picks (options dense_pp, dense_var, dense_scan_nt, dense_rot)
+struct ErhPpMode {
+    bool lean;                                // the lean-issue kernel: X must be padded by kDensePadRows zero rows (false: a matrix that is not)
+    bool strict;                              // strict alternation (dense_pp 3): what the half query tile, the nt hint and the sample pass need
+    int var;                                  // option dense_var, or 2 for the tiled chunk operand
+    bool nt;                                  // chunk-side loads with the non-temporal hint where every chunk row has one reader
+    int rot_stages;                           // K-rotation between the query tiles of a stream
+};
+hipError_t launch_dense_scan_append(int cfg, const ErhScanArgs &a, int ablate, unsigned long long *dbg, hipStream_t st);
+hipError_t launch_dense_scan_pp(const ErhScanArgs &a, int n_cus, int pabl, unsigned long long *dbg, const ErhPpMode &mode,
                                 uint32_t *stream_sync /* dense_pp 3: 256 zeroed words (one per stream) or null */,
                                 const ErhSeedIo *sio /* null, or the sample pass (dense_pp 3 only) */,
                                 hipStream_t st);
-// 384 x 256 ping-pong scan over tiled operands (dense_scan_pp5_kernel; batches padded to >= 512 queries): Xt from
-// launch_dense_tile_rows_n(X, N, d, dense_scan_pp5_rows(), ...) -- ceil(N / 384) * 384 * d halves --, Qt from launch_dense_tile_rows of
+// 384 x 256 ping-pong scan over tiled operands (dense_scan_pp5_kernel; batches padded to >= 512 queries): a.X from
+// launch_dense_tile_rows_n(X, N, d, dense_scan_pp5_rows(), ...) -- ceil(N / 384) * 384 * d halves --, a.Q from launch_dense_tile_rows of
 // the query block; c0 a multiple of 384.  hipErrorInvalidValue when the shape does not qualify (the caller falls through).
 int dense_scan_pp5_rows();
 hipError_t launch_dense_tile_rows_n(const _Float16 *X, int64_t N, int d, int rows, void *Xt, hipStream_t st);
-hipError_t launch_dense_scan_pp5(const _Float16 *Xt, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Qt,
-                                 int Bpad, int B, const float *tau, const int16_t *filter_dir, const int16_t *dir_id,
-                                 ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus, int rot_stages,
-                                 hipStream_t st);
+hipError_t launch_dense_scan_pp5(const ErhScanArgs &a, int n_cus, int rot_stages, hipStream_t st);
 // tiled copy of the chunk matrix for the ping-pong scan: ceil(N / 256) * 256 * d halves (see dense_tile_rows_kernel)
 hipError_t launch_dense_tile_rows(const _Float16 *X, int64_t N, int d, void *Xt, hipStream_t st);
-hipError_t launch_dense_scan_pp4(const _Float16 *Xt, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Qt,
-                                 int Bpad, int B, const float *tau, const int16_t *filter_dir, const int16_t *dir_id,
-                                 ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus, int pabl,
-                                 unsigned long long *dbg, int rot_stages, hipStream_t st);
 constexpr int kDensePadRows = 384;   // zero rows erh_set_dense keeps behind the matrix (tiles past N read them: up to 383 for the 384-row tile)
-hipError_t launch_dense_scan_persist(int cfg, const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1,
-                                     const _Float16 *Q, int Bpad, int B, const float *tau,
-                                     const int16_t *filter_dir, const int16_t *dir_id,
-                                     ErhCand *cand, uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus,
-                                     int pabl, int readahead, hipStream_t st);
+#ifdef ERH_MEASURE   // earlier generations of the scan, kept as measurement arms (a.X / a.Q of pp4: the tiled copies)
+hipError_t launch_dense_scan_pp4(const ErhScanArgs &a, int n_cus, int pabl, unsigned long long *dbg, int rot_stages, hipStream_t st);
+hipError_t launch_dense_scan_persist(int cfg, const ErhScanArgs &a, int n_cus, int pabl, int readahead, hipStream_t st);
+#endif
 hipError_t launch_dense_naive(const _Float16 *Q, int B, const _Float16 *X, int64_t row0, int rows, int d,
                               float *out, hipStream_t st);
 
 // ---- dense_gemv.hip: append scan for batches of at most dense_gemv_max_queries() queries ----------------------------
 int dense_gemv_max_queries();
 hipError_t dense_gemv_init();
-hipError_t launch_dense_gemv_append(const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Q, int B,
-                                    const float *tau, const int16_t *filter_dir, const int16_t *dir_id, ErhCand *cand,
-                                    uint32_t *cand_cnt, int cap, uint32_t *overflow, int n_cus, int kb, int wgs,
-                                    int pipe, hipStream_t st, int nt = 0 /* chunk loads with the non-temporal hint (option dense_gemv_nt) */);
+hipError_t launch_dense_gemv_append(const ErhScanArgs &a /* Bpad is not read: the stream takes the B queries as they are */, int n_cus, int kb,
+                                    int wgs, int pipe, hipStream_t st, int nt = 0 /* chunk loads with the non-temporal hint (option dense_gemv_nt) */);
 hipError_t launch_dense_gemv_store(const _Float16 *X, int64_t N, int d, int64_t c0, int nc, const _Float16 *Q, int B,
                                    float *S0, int ld_s0, int n_cus, int kb, int wgs, int pipe, hipStream_t st);
 

@@ -12,71 +12,81 @@ static int dense_rot_stages(const erh_handle *h, int d, int Bpad) {
     return n_qt > 1 ? (nk / n_qt) & ~1 : 0;
 }
 
+// What launch_dense_scan_pp is asked for on matrix X.  A matrix that is not the view's own (a gathered block of debug rows) has no zero padding
+// behind it, and neither has anything below dense_pp 2 asked for it: the mode stays empty.
+static erh::ErhPpMode dense_pp_mode(const erh_handle *h, bool own_x, int var, int d, int Bpad) {
+    erh::ErhPpMode m{};
+    if (h->opt_dense_pp >= 2 && own_x) {
+        m.lean = true;
+        m.strict = h->opt_dense_pp >= 3;
+        m.var = var;
+        m.nt = h->opt_dense_scan_nt != 0;
+        m.rot_stages = dense_rot_stages(h, d, Bpad);
+    }
+    return m;
+}
+
 // Append-stage scan: persistent kernel when enabled and applicable, else one workgroup per tile.
-static hipError_t scan_append(erh_handle *h, const _Float16 *X, int64_t N, int d, int64_t c0, int64_t c1, const _Float16 *Q16,
-                       int Bpad, int B, const float *tau, const int16_t *filt, const int16_t *dir, ErhCand *cand,
-                       uint32_t *cnt, int cap, uint32_t *flags, hipStream_t st) {
+static hipError_t scan_append(erh_handle *h, const erh::ErhScanArgs &a, hipStream_t st) {
+    const int B = a.B, Bpad = a.Bpad, d = a.d;
+    const int64_t c0 = a.c0, c1 = a.c1;
     // small batches: the skinny-GEMM stream (dense_gemv.hip) instead of a 256-query tile that is mostly padding
     if (h->opt_dense_gemv && h->opt_dense_ablate == 0 && B <= erh::dense_gemv_max_queries()) {
-        hipError_t e = erh::launch_dense_gemv_append(X, N, d, c0, c1, Q16, B, tau, filt, dir, cand, cnt, cap, flags,
-                                                     h->n_cus, h->opt_gemv_kb, h->opt_gemv_wgs, h->opt_gemv_pipe, st,
+        hipError_t e = erh::launch_dense_gemv_append(a, h->n_cus, h->opt_gemv_kb, h->opt_gemv_wgs, h->opt_gemv_pipe, st,
                                                      h->opt_gemv_nt >= 0 ? h->opt_gemv_nt : (!h->sparse_beside && B <= 32) ? 1 : 0);
         if (e != hipErrorInvalidValue) { h->stats.dense_scan_gemv += (c1 > c0); return e; }
         (void)hipGetLastError();
     }
     const int abl = h->opt_dense_ablate;
     const bool pp_code = abl == 0 || abl == 7 || abl == 8 || (abl >= 11 && abl <= 18) || (abl >= 20 && abl <= 24);
-    const bool own_x = X == h->view.X;                        // the view's matrix itself (padded; not a gathered block of debug rows)
+    const bool own_x = a.X == h->view.X;                      // the view's matrix itself (padded; not a gathered block of debug rows)
     const bool global_x = own_x && h->view.global;            // ... and the handle's whole matrix: its tiled copies apply
+    unsigned long long *dbg = h->opt_debug_counters ? h->dbg.as<unsigned long long>() : nullptr;
+    erh::ErhScanArgs t = a;                                   // the same scan over tiled copies of the operands
     if (h->qt5_valid && h->xt384_valid && abl == 0 && global_x) {
         // 384 x 256 tile over the tiled copies (the caller checked the options and built the copies)
-        hipError_t e = erh::launch_dense_scan_pp5(h->Xt384.as<_Float16>(), N, d, c0, c1, h->Qt.as<_Float16>(), Bpad, B, tau, filt,
-                                                  dir, cand, cnt, cap, flags, h->n_cus,
+        t.X = h->Xt384.as<_Float16>(); t.Q = h->Qt.as<_Float16>();
+        hipError_t e = erh::launch_dense_scan_pp5(t, h->n_cus,
                                                   h->opt_dense_rot >= 0 ? h->opt_dense_rot : 0 /* the workgroups of a stream on the same stage: measured best here (profiles/r04w_kbench_tile384.log) */, st);
         if (e != hipErrorInvalidValue) { h->stats.dense_scan_pp5 += (c1 > c0); return e; }
         (void)hipGetLastError();
     }
+#ifdef ERH_MEASURE
     if (h->opt_dense_pp >= 4 && pp_code && global_x && h->xt_valid && h->qt_valid) {
         // both operands from their tiled copies (dense_scan_pp4_kernel)
-        hipError_t e = erh::launch_dense_scan_pp4(h->Xt.as<_Float16>(), N, d, c0, c1, h->Qt.as<_Float16>(), Bpad, B, tau, filt,
-                                                  dir, cand, cnt, cap, flags, h->n_cus, h->opt_dense_ablate,
-                                                  h->opt_debug_counters ? h->dbg.as<unsigned long long>() : nullptr,
+        t.X = h->Xt.as<_Float16>(); t.Q = h->Qt.as<_Float16>();
+        hipError_t e = erh::launch_dense_scan_pp4(t, h->n_cus, abl, dbg,
                                                   h->opt_dense_rot >= 0 ? h->opt_dense_rot : (Bpad > erh::dense_scan_q_tile() ? (d / 32) / (Bpad / erh::dense_scan_q_tile()) : 0),
                                                   st);
         if (e != hipErrorInvalidValue) return e;
         (void)hipGetLastError();
     }
+#endif
     if (h->opt_dense_pp && pp_code) {
-        const bool own = own_x;
         const int QT = erh::dense_scan_q_tile();
         // the strict ping-pong kernel streams the tiled copy when there is one and the stage starts on a tile boundary
         const bool tiled = global_x && h->opt_dense_pp >= 3 && h->opt_dense_tiled && h->xt_valid && h->opt_dense_var == 0 &&
                            c0 % QT == 0;
-        const int var = tiled ? 2 : h->opt_dense_var;
         uint32_t *sync = nullptr;
-        if (h->opt_dense_sync && h->opt_dense_pp >= 3 && own && Bpad > QT) {
+        if (h->opt_dense_sync && h->opt_dense_pp >= 3 && own_x && Bpad > QT) {
             if (h->scan_sync.ensure(1024) == hipSuccess && hipMemsetAsync(h->scan_sync.p, 0, 1024, st) == hipSuccess)
                 sync = h->scan_sync.as<uint32_t>();
         }
-        hipError_t e = erh::launch_dense_scan_pp(tiled ? h->Xt.as<_Float16>() : X, N, d, c0, c1, Q16, Bpad, B, tau, filt, dir,
-                                                 cand, cnt, cap, flags, h->n_cus, h->opt_dense_ablate,
-                                                 h->opt_debug_counters ? h->dbg.as<unsigned long long>() : nullptr,
-                                                 (h->opt_dense_pp >= 2 && own)
-                                                     ? (1 | (var << 1) | (h->opt_dense_pp >= 3 ? 8 : 0) | (h->opt_dense_scan_nt ? 16 : 0) | (dense_rot_stages(h, d, Bpad) << 8)) : 0,
-                                                 sync, nullptr, st);
+        t.X = tiled ? h->Xt.as<_Float16>() : a.X; t.Q = a.Q;
+        hipError_t e = erh::launch_dense_scan_pp(t, h->n_cus, abl, dbg, dense_pp_mode(h, own_x, tiled ? 2 : h->opt_dense_var, d, Bpad), sync,
+                                                 nullptr, st);
         if (e != hipErrorInvalidValue) { h->stats.dense_scan_pp3 += (c1 > c0); return e; }
         (void)hipGetLastError();
     }
-    if (h->opt_dense_persist && (h->opt_dense_ablate == 0 || h->opt_dense_ablate >= 6)) {
-        hipError_t e = erh::launch_dense_scan_persist(h->opt_dense_cfg, X, N, d, c0, c1, Q16, Bpad, B, tau, filt, dir, cand,
-                                                      cnt, cap, flags, h->n_cus, h->opt_dense_ablate, h->opt_dense_readahead, st);
+#ifdef ERH_MEASURE
+    if (h->opt_dense_persist && (abl == 0 || abl >= 6)) {
+        hipError_t e = erh::launch_dense_scan_persist(h->opt_dense_cfg, a, h->n_cus, abl, h->opt_dense_readahead, st);
         if (e != hipErrorInvalidValue) { h->stats.dense_scan_tile += (c1 > c0); return e; }
         (void)hipGetLastError();
     }
+#endif
     h->stats.dense_scan_tile += (c1 > c0);
-    return erh::launch_dense_scan_append(h->opt_dense_cfg, X, N, d, c0, c1, Q16, Bpad, B, tau, filt, dir, cand, cnt, cap,
-                                         flags, h->opt_dense_ablate,
-                                         h->opt_debug_counters ? h->dbg.as<unsigned long long>() : nullptr, st);
+    return erh::launch_dense_scan_append(h->opt_dense_cfg, a, abl, dbg, st);
 }
 
 // A fused call's side of the final kernel's hybrid mode (handle.h: HybridLazy)
@@ -231,6 +241,11 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
             dir = h->dir_pos.as<int16_t>();
         }
     }
+    erh::ErhScanArgs sa{};                        // the append stage's operands; every scan below sets its rows [c0, c1)
+    sa.X = X; sa.N = N; sa.d = d;
+    sa.Q = Q16; sa.Bpad = Bpad; sa.B = B;
+    sa.tau = h->tau.as<float>(); sa.filter_dir = filter_dev; sa.dir_id = dir;
+    sa.cand = h->cand.as<ErhCand>(); sa.cand_cnt = h->cand_cnt.as<uint32_t>(); sa.cap = cap; sa.overflow = flags;
     auto scan_work = [&](int64_t rows, double *bytes, double *flops) {
         *bytes = (double)rows * d * 2.0 + (double)Bpad * d * 2.0;
         *flops = 2.0 * (double)rows * (double)Bpad * (double)d;
@@ -273,20 +288,21 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
             HIPCHK(h, h->seed_top.ensure((size_t)Bpad * n_vals * 4));
             sio.seed_top = h->seed_top.as<float>();
             h->stats.dense_sample_passes += 1;
-            const int lean = 1 | 8 | (dense_rot_stages(h, d, Bpad) << 8);
+            erh::ErhPpMode pm{};                  // the strict kernel's row-major plain variant, whatever the options say
+            pm.lean = pm.strict = true;
+            pm.rot_stages = dense_rot_stages(h, d, Bpad);
             // (the pass books no work: the sampled rows are scanned again below, and N rows are what the algorithm needs; its own class)
             { ProfScope ps(h, st, ERH_K_DENSE_SAMPLE, 0, 0);
-              HIPCHK(h, erh::launch_dense_scan_pp(X, N, d, 0, rows_seed, Q16, Bpad, B, h->tau.as<float>(), nullptr, nullptr,
-                                                  h->cand.as<ErhCand>(), h->cand_cnt.as<uint32_t>(), cap, flags, h->n_cus, 0,
-                                                  nullptr, lean, nullptr, &sio, st)); }
+              sa.c0 = 0; sa.c1 = rows_seed;
+              HIPCHK(h, erh::launch_dense_scan_pp(sa, h->n_cus, 0, nullptr, pm, nullptr, &sio, st)); }
             { ProfScope ps(h, st, ERH_K_DENSE_SELECT, 0, 0);
               HIPCHK(h, erh::launch_seed_cells_select(sio.seed_top, n_vals, B, rank, h->qnorm.as<float>(), h->xnorm_max, d,
                                                       h->tau.as<float>(), h->cand_cnt.as<uint32_t>(), st)); }
             scan_work(N, &wb, &wf);
             int rc_scan = ERH_OK;
             { ProfScope ps(h, st, ERH_K_DENSE_SCAN, wb, wf);
-              hipError_t e = scan_append(h, X, N, d, 0, N, Q16, Bpad, B, h->tau.as<float>(), nullptr, nullptr,
-                                         h->cand.as<ErhCand>(), h->cand_cnt.as<uint32_t>(), cap, flags, st);
+              sa.c1 = N;
+              hipError_t e = scan_append(h, sa, st);
               if (e != hipSuccess) rc_scan = h->fail(ERH_ERR_HIP, "dense scan behind the sample pass", e); }
             if (rc_scan != ERH_OK) return rc_scan;
             if (h->fork_after_scan) HIPCHK(h, hipEventRecord(h->ev_fork, st));
@@ -372,9 +388,9 @@ int dense_topk_dev(erh_handle *h, const void *q_dev, int q_dtype, int normalize_
                 if (b > cur && b < N) next = b;
             }
             scan_work(next - cur, &wb, &wf);
+            sa.c0 = cur; sa.c1 = next;
             { ProfScope ps(h, st, ERH_K_DENSE_SCAN, wb, wf);
-              HIPCHK(h, scan_append(h, X, N, d, cur, next, Q16, Bpad, B, h->tau.as<float>(), filter_dev, dir,
-                                     h->cand.as<ErhCand>(), h->cand_cnt.as<uint32_t>(), cap, flags, st)); }
+              HIPCHK(h, scan_append(h, sa, st)); }
             if (next < N) {
                 ProfScope ps(h, st, ERH_K_DENSE_SELECT, 0, 0);
                 HIPCHK(h, erh::launch_cand_refine(B, k, h->qnorm.as<float>(), h->xnorm_max, d, h->tau.as<float>(),

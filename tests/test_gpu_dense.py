@@ -404,6 +404,36 @@ def test_dense_cache_policy_and_occupancy_arms(engine, b, k):
         assert np.array_equal(sc[i].view(np.uint64), osc.view(np.uint64)), f"query {i}: fp64 scores differ"
 
 
+def test_dense_sample_pass_on_the_half_query_tile(engine):
+    """The sample pass of a batch of 65 ... 128 queries: the half-query-tile instantiation of the sample pass (kernel trace:
+    dense_scan_pp3_kernel<0, 24>), which no other test launches (profiles/pp3_variants_suite.txt).  One query tile takes the sample pass
+    only with dense_selfseed = 2, where the first ceil(n0 / 256) chunk streams take one tile each, and only when the host's rule holds
+    (pipeline_dense.hip): rank = erh_dense_seed_rank(k, rows, n) < k and 4 * rank <= cells = rows / 64.  At k = 10 that needs rank = 9,
+    rows = 9 * 256 = 2304 and 10 * 2304 / n <= 0.672, i.e. n >= 34291: the smallest corpus that reaches the kernel, not the few thousand
+    rows that reach the other variants.  d = 256 is the kernel's minimum of 8 stages; n is no multiple of the tile.  Ids and fp64 scores
+    against the oracle bit for bit."""
+    n, d, b, k = 34_500, 256, 100, 10
+    x = synth.dense_corpus(n, d, seed=701)
+    q16 = to_f16_unit(synth.dense_queries(x, b, seed=702))
+    engine.set_option("dense_selfseed", 2)
+    engine.set_option("dense_n0", 2304)
+    try:
+        engine.set_dense(x)
+        engine.reset_stats()
+        ids, sc, ln = engine.dense_topk(q16, k)
+        st, diag = engine.stats(), engine.dense_diag()
+    finally:
+        engine.set_option("dense_n0", 32768)
+        engine.set_option("dense_selfseed", 1)
+    assert st["dense_sample_passes"] == 1 and st["dense_scan_pp3_launches"] == 1 and st["dense_scan_gemv_launches"] == 0, st
+    assert diag["uncertified"] == 0 and diag["max_abs_err"] <= diag["margin"] and diag["exhaustive"] == 0, diag
+    assert np.all(ln == k)
+    for i in (0, 1, 31, 32, 63, 64, 98, 99):                     # both ends of the wave columns of the half tile
+        oid, osc = dense_exact_topk(x, q16[i], k)
+        assert np.array_equal(ids[i], oid), f"query {i}: ids differ"
+        assert np.array_equal(sc[i].view(np.uint64), osc.view(np.uint64)), f"query {i}: fp64 scores differ"
+
+
 def test_dense_sample_pass_with_a_cell_full_of_copies(engine):
     """Eight copies of the chunk a query asks for, planted in ONE cell of the sampled rows (stored rows 0-3 and 8-11 of tile 0:
     one lane of one wave holds them; dense_shuffle = 0 keeps the caller's order).  The cell shows the sample only two of them

@@ -513,3 +513,71 @@ def test_grouped_launch_sample_pass(engine):
         engine.set_option("dense_group_launch", 1)
         engine.set_option("dense_dir_blocks", 1)
         engine.set_doc_meta(n, None, None)
+
+
+@pytest.mark.parametrize("counts", [(50, 50), (200, 100)], ids=["half-query-tiles", "a-whole-query-tile"])
+def test_grouped_scan_with_the_nt_hint(engine, counts):
+    """The grouped scan with chunk-side non-temporal loads (dense_scan_nt = 1) has instantiations of its own -- kernel trace:
+    dense_scan_pp3_kernel<0, 104> when no query tile holds more than 128 queries, <0, 96> otherwise -- and a block that fits the seed
+    prefix never reaches the scan, so no other test launches them (profiles/pp3_variants_suite.txt).  Two blocks of 4100 and 4700 rows (no
+    multiples of the tile), d = 256 (the kernel's minimum of 8 stages), a seed prefix of 1024 rows so that the scan has rows left, k = 10;
+    100 queries as two half tiles, 300 as a whole tile and a half one.  Same lists as without the hint; ids and fp64 scores against the
+    oracle bit for bit."""
+    rng = np.random.default_rng(1301)
+    sizes = [4100, 4700]
+    n, d, b, k = sum(sizes), 256, sum(counts), 10
+    x = to_f16_unit(rng.standard_normal((n, d), dtype=np.float32) + 0.3 * rng.standard_normal(d).astype(np.float32))
+    dir_id = _blocks(sizes)
+    filt = rng.permutation(np.repeat(np.arange(2), counts)).astype(np.int16)
+    q16 = to_f16_unit(x[rng.integers(0, n, b)].astype(np.float32) + 0.4 * rng.standard_normal((b, d), dtype=np.float32))
+    engine.set_option("dense_dir_blocks", 2)
+    engine.set_option("dense_n0", 1024)
+    try:
+        engine.set_dense(x)
+        engine.set_doc_meta(n, None, dir_id)
+        plain = engine.dense_topk(q16, k, filter_dir=filt)
+        engine.set_option("dense_scan_nt", 1)
+        engine.reset_stats()
+        got = engine.dense_topk(q16, k, filter_dir=filt)
+        st, diag = engine.stats(), engine.dense_diag()
+        assert st["dense_grouped_launches"] == 1 and st["dense_block_groups"] == 2 and st["dense_scan_pp3_launches"] == 1, st
+        assert diag["uncertified"] == 0 and diag["max_abs_err"] <= diag["margin"], diag
+        _same(plain, got)
+        _check_oracle(x, q16, k, dir_id, filt, got, (0, 1, 2, 3, b // 2, b - 2, b - 1))
+    finally:
+        engine.set_option("dense_scan_nt", 0)
+        engine.set_option("dense_n0", 32768)
+        engine.set_option("dense_dir_blocks", 1)
+        engine.set_doc_meta(n, None, None)
+
+
+def test_grouped_sample_pass_on_half_query_tiles(engine):
+    """The grouped sample pass when no query tile holds more than 128 queries (kernel trace: dense_scan_pp3_kernel<0, 56>), which no other
+    test launches (profiles/pp3_variants_suite.txt).  The host plans a sample pass only where every view qualifies (pipeline_dense.hip):
+    sampled rows >= N / 4 of a view below 65536 rows, at most N / 2, and erh_dense_seed_rank(k, rows, N) < k.  A quarter of the view gives
+    mu = k / 4, so k = 10 never qualifies below N = 186 k per view (rank 16 >= k); k = 100 does (mu = 33, rank 74), and "at most N / 2"
+    needs three rounds of chunk tiles, i.e. more than 512 tiles over the views on 256 compute units: two blocks of 66 000 and 70 000 rows
+    are about the smallest shape that reaches the kernel.  d = 256 (the kernel's minimum of 8 stages), 100 queries as two half tiles.  Same
+    lists as the filter column on the whole matrix; ids and fp64 scores against the oracle bit for bit."""
+    rng = np.random.default_rng(1302)
+    sizes = [66_000, 70_000]
+    n, d, b, k = sum(sizes), 256, 100, 100
+    x = to_f16_unit(rng.standard_normal((n, d), dtype=np.float32) + 0.3 * rng.standard_normal(d).astype(np.float32))
+    dir_id = _blocks(sizes)
+    filt = (np.arange(b) % 2).astype(np.int16)
+    q16 = to_f16_unit(x[rng.integers(0, n, b)].astype(np.float32) + 0.4 * rng.standard_normal((b, d), dtype=np.float32))
+    engine.set_option("dense_dir_blocks", 2)
+    try:
+        engine.set_dense(x)
+        engine.set_doc_meta(n, None, dir_id)
+        engine.reset_stats()
+        got = engine.dense_topk(q16, k, filter_dir=filt)
+        st, diag = engine.stats(), engine.dense_diag()
+        assert st["dense_grouped_launches"] == 1 and st["dense_sample_passes"] == 1 and st["dense_scan_pp3_launches"] == 1, st
+        assert diag["uncertified"] == 0 and diag["exhaustive"] == 0 and diag["max_abs_err"] <= diag["margin"], diag
+        engine.set_option("dense_dir_blocks", 0)
+        _same(engine.dense_topk(q16, k, filter_dir=filt), got)
+        _check_oracle(x, q16, k, dir_id, filt, got, (0, 1, 2, 49, 98, 99))
+    finally:
+        engine.set_option("dense_dir_blocks", 1)
+        engine.set_doc_meta(n, None, None)
