@@ -286,7 +286,9 @@ int erh_get_stat(erh_handle *h, const char *name, int64_t *value) {
         {"dense_grouped_launches", T.dense_grouped_launches}, {"bm25_mixed_launches", T.bm25_mixed_launches},
         {"dense_rows_calls", T.dense_rows_calls}, {"dense_rows_short_launches", T.dense_rows_short}, {"dense_rows_long_launches", T.dense_rows_long},
         {"dense_group_reruns", T.dense_group_reruns}, {"bm25_rows_calls", T.bm25_rows_calls},
-        {"bm25_rows_short_launches", T.bm25_rows_short}, {"bm25_rows_long_launches", T.bm25_rows_long}};
+        {"bm25_rows_short_launches", T.bm25_rows_short}, {"bm25_rows_long_launches", T.bm25_rows_long},
+        {"bm25_sets_calls", T.bm25_sets_calls}, {"bm25_sets_subqueries", T.bm25_sets_subqueries},
+        {"bm25_sets_merge_launches", T.bm25_sets_merge_launches}};
     for (const auto &e : host)
         if (!strcmp(name, e.n)) { *value = e.v; return ERH_OK; }
     if (!strcmp(name, "dense_candidates_last_call")) {
@@ -962,42 +964,40 @@ int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, i
 // class, an empty set none.  erh_dense_check -> dense_sets_check: the sub-queries' flag words, and the merge again if they changed a list.
 static constexpr int kSetsChunk = 8192;
 
-int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
-                        int B, int k, const int32_t *set_ptr, const int16_t *set_cls, int mode,
-                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
-    if (!h) return ERH_ERR_INVALID;
-    int rc = check_dense_args(h, "erh_dense_topk_sets", q, out_ids && out_scores && out_len && set_ptr, B, k, q_dtype, mode);
-    if (rc != ERH_OK) return rc;
-    // the CSR: monotone, classes >= 0 (32767 = matches nothing) and distinct within a set, or the set {-1} alone
-    if (set_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: set_ptr[0] != 0");
+// The class-set CSR of the two sets entries (erh_dense_topk_sets, erh_bm25_topk_sets): monotone from 0, classes >= 0 (32767 = matches
+// nothing) and distinct within a set, or the set {-1} alone; a set that names a class needs a class column over all n_docs documents.
+static int check_class_sets(erh_handle *h, const char *who, const int32_t *set_ptr, const int16_t *set_cls, int B, int64_t n_docs) {
+    const std::string w(who);
+    if (set_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, (w + ": set_ptr[0] != 0").c_str());
     for (int b = 0; b < B; ++b)
-        if (set_ptr[b + 1] < set_ptr[b]) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: set_ptr not monotone");
-    if (set_ptr[B] > 0 && !set_cls) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: null set_cls");
+        if (set_ptr[b + 1] < set_ptr[b]) return h->fail(ERH_ERR_INVALID, (w + ": set_ptr not monotone").c_str());
+    if (set_ptr[B] > 0 && !set_cls) return h->fail(ERH_ERR_INVALID, (w + ": null set_cls").c_str());
     bool any_class = false;
-    {
-        std::vector<int16_t> tmp;
-        for (int b = 0; b < B; ++b) {
-            const int m = set_ptr[b + 1] - set_ptr[b];
-            const int16_t *c = set_cls + set_ptr[b];
-            if (m == 1 && c[0] == -1) continue;
-            tmp.assign(c, c + m);
-            std::sort(tmp.begin(), tmp.end());
-            for (int i = 0; i < m; ++i) {
-                if (tmp[i] < 0) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: negative class (only the set {-1} means unfiltered)");
-                if (i && tmp[i] == tmp[i - 1]) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_sets: a class twice in one set");
-            }
-            any_class = any_class || m > 0;
+    std::vector<int16_t> tmp;
+    for (int b = 0; b < B; ++b) {
+        const int m = set_ptr[b + 1] - set_ptr[b];
+        const int16_t *c = set_cls + set_ptr[b];
+        if (m == 1 && c[0] == -1) continue;
+        tmp.assign(c, c + m);
+        std::sort(tmp.begin(), tmp.end());
+        for (int i = 0; i < m; ++i) {
+            if (tmp[i] < 0) return h->fail(ERH_ERR_INVALID, (w + ": negative class (only the set {-1} means unfiltered)").c_str());
+            if (i && tmp[i] == tmp[i - 1]) return h->fail(ERH_ERR_INVALID, (w + ": a class twice in one set").c_str());
         }
+        any_class = any_class || m > 0;
     }
-    if (any_class && (!h->has_dir || h->Nmeta < h->N))
-        return h->fail(ERH_ERR_STATE, "erh_dense_topk_sets: set filter given but erh_set_doc_meta(dir_id) not set for all documents");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    // the sub-query batch: a class that no document carries (32767, or beyond the classes erh_set_doc_meta saw) contributes nothing and
-    // gets no sub-query; an unfiltered query one without a class
+    if (any_class && (!h->has_dir || h->Nmeta < n_docs))
+        return h->fail(ERH_ERR_STATE, (w + ": set filter given but erh_set_doc_meta(dir_id) not set for all documents").c_str());
+    return ERH_OK;
+}
+
+// ... and its sub-query batch: source query and class of every sub-query, query b's sub-queries at sub_ptr[b] .. sub_ptr[b + 1].  A class
+// that no document carries (32767, or beyond the classes erh_set_doc_meta saw) contributes nothing and gets no sub-query; an unfiltered
+// query gets one without a class.
+static void expand_class_sets(const erh_handle *h, const int32_t *set_ptr, const int16_t *set_cls, int B, std::vector<int32_t> &sub_ptr,
+                              std::vector<int32_t> &src, std::vector<int16_t> &cls) {
     const int nc = (int)h->dir_cnt_h.size();
-    std::vector<int32_t> sub_ptr((size_t)B + 1, 0), src;
-    std::vector<int16_t> cls;
+    sub_ptr.assign((size_t)B + 1, 0);
     for (int b = 0; b < B; ++b) {
         const int m = set_ptr[b + 1] - set_ptr[b];
         const int16_t *c = set_cls ? set_cls + set_ptr[b] : nullptr;
@@ -1007,6 +1007,21 @@ int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_devi
                 if (c[i] < nc && h->dir_cnt_h[c[i]] > 0) { src.push_back(b); cls.push_back(c[i]); }
         sub_ptr[(size_t)b + 1] = (int32_t)src.size();
     }
+}
+
+int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
+                        int B, int k, const int32_t *set_ptr, const int16_t *set_cls, int mode,
+                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
+    if (!h) return ERH_ERR_INVALID;
+    int rc = check_dense_args(h, "erh_dense_topk_sets", q, out_ids && out_scores && out_len && set_ptr, B, k, q_dtype, mode);
+    if (rc != ERH_OK) return rc;
+    rc = check_class_sets(h, "erh_dense_topk_sets", set_ptr, set_cls, B, h->N);
+    if (rc != ERH_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t> sub_ptr, src;
+    std::vector<int16_t> cls;
+    expand_class_sets(h, set_ptr, set_cls, B, sub_ptr, src, cls);
     const int n_sub = (int)src.size();
     const size_t off_src = ((size_t)B + 1) * 4, off_cls = off_src + (size_t)n_sub * 4;
     {
@@ -1333,6 +1348,92 @@ int erh_bm25_topk_rows(erh_handle *h, const int32_t *q_indptr, const int32_t *q_
     h->stats.bm25_rows_calls += 1;
     const int rc = bm25_rows_dev(h, P, k, out.d_ids, out.d_sc, out.d_len, st);
     return rc == ERH_OK ? out.finish(st) : rc;
+}
+
+// Set filters on the sparse route, the twin of erh_dense_topk_sets: every (query, allowed class) pair is a sub-query of ordinary class-column
+// batches through upload_bm25_queries + bm25_topk_dev (chunks of kBm25SetsChunk sub-queries, one behind the other on the stream), whose
+// lists go to bs_ids / bs_sc / bs_len; then ONE merge launch (bm25_sets.hip) builds each query's list from its sub-lists -- after the last
+// chunk, since a query's sub-queries may straddle a chunk boundary.  An unfiltered query ({-1}) is one sub-query without a class, an empty
+// set none, a class no document carries none.  Everything is checked on the host before anything is enqueued; no flag words are set.
+static constexpr int kBm25SetsChunk = 8192;
+
+int erh_bm25_topk_sets(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
+                       const int32_t *set_ptr, const int16_t *set_cls,
+                       int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
+    if (!h) return ERH_ERR_INVALID;
+    const Bm25State &S = h->bm[h->cur];
+    if (S.variant < 0) return h->fail(ERH_ERR_STATE, "erh_bm25_topk_sets before erh_set_bm25_*");
+    if (!q_indptr || !set_ptr || !out_ids || !out_scores || !out_len || B <= 0)
+        return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: null pointer or non-positive B");
+    if (k < 1 || k > 1024) return h->fail(ERH_ERR_UNSUPPORTED, "erh_bm25_topk_sets: k outside [1, 1024]");
+    // the queries, as erh_bm25_topk takes them
+    if (q_indptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: q_indptr[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        if (q_indptr[b + 1] < q_indptr[b]) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: q_indptr must be non-decreasing");
+    const int nt = q_indptr[B];
+    if (nt > 0 && !q_tok) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: null q_tok");
+    for (int i = 0; i < nt; ++i)
+        if (q_tok[i] < 0 || q_tok[i] >= S.V) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: query term id out of range");
+    // the sets, as erh_dense_topk_sets takes them, and the sub-query batch they stand for
+    const int rc_sets = check_class_sets(h, "erh_bm25_topk_sets", set_ptr, set_cls, B, S.Nb);
+    if (rc_sets != ERH_OK) return rc_sets;
+    std::vector<int32_t> sub_ptr, src;
+    std::vector<int16_t> cls;
+    expand_class_sets(h, set_ptr, set_cls, B, sub_ptr, src, cls);
+    const int n_sub = (int)src.size();
+    for (int c0 = 0; c0 < n_sub; c0 += kBm25SetsChunk) {             // a chunk's query CSR has 32-bit offsets
+        int64_t toks = 0;
+        for (int i = c0; i < std::min(n_sub, c0 + kBm25SetsChunk); ++i) toks += q_indptr[src[i] + 1] - q_indptr[src[i]];
+        if (toks > 2147483647LL) return h->fail(ERH_ERR_UNSUPPORTED, "erh_bm25_topk_sets: more than 2^31 query tokens in one chunk of sub-queries");
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    // buffers first: a call that cannot have them enqueues nothing
+    HostOut out(h, out_ids, out_scores, out_len, out_is_device, B, k);
+    {
+        hipError_t e = h->bs_tab.ensure(((size_t)B + 1) * 4);
+        if (e == hipSuccess && n_sub > 0) e = h->bs_ids.ensure((size_t)n_sub * k * 4);
+        if (e == hipSuccess && n_sub > 0) e = h->bs_sc.ensure((size_t)n_sub * k * 8);
+        if (e == hipSuccess && n_sub > 0) e = h->bs_len.ensure((size_t)n_sub * 4);
+        if (e == hipSuccess) e = out.ensure();
+        if (e != hipSuccess) { (void)hipGetLastError(); return h->fail(ERH_ERR_NOMEM, "erh_bm25_topk_sets: work space", e); }
+    }
+    HIPCHK(h, hipMemcpyAsync(h->bs_tab.p, sub_ptr.data(), ((size_t)B + 1) * 4, hipMemcpyHostToDevice, st));
+    // (`sub_ptr` is pageable memory of this scope -- and whatever was enqueued in front of this call has now read the query staging
+    // (qpack_host) that the first chunk is about to overwrite)
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->stats.bm25_calls += 1;
+    h->stats.bm25_sets_calls += 1;
+    h->stats.bm25_sets_subqueries += n_sub;
+    std::vector<int32_t> c_ptr, c_tok;
+    for (int c0 = 0; c0 < n_sub; c0 += kBm25SetsChunk) {
+        const int nb = std::min(kBm25SetsChunk, n_sub - c0);
+        c_ptr.assign((size_t)nb + 1, 0);
+        c_tok.clear();
+        bool filtered = false;
+        for (int i = 0; i < nb; ++i) {
+            const int b = src[(size_t)c0 + i];
+            if (q_indptr[b + 1] > q_indptr[b]) c_tok.insert(c_tok.end(), q_tok + q_indptr[b], q_tok + q_indptr[b + 1]);
+            c_ptr[(size_t)i + 1] = (int32_t)c_tok.size();
+            filtered = filtered || cls[(size_t)c0 + i] >= 0;
+        }
+        // the upload below rewrites the host staging of the query CSR: the previous chunk's copy must have read it
+        if (c0 > 0) HIPCHK(h, hipStreamSynchronize(st));
+        double bytes = 0;
+        int max_qlen = 0;
+        const int16_t *filt = nullptr;
+        int rc = upload_bm25_queries(h, c_ptr.data(), c_tok.data(), nb, st, S.host_indptr, &bytes, &max_qlen,
+                                     filtered ? cls.data() + c0 : nullptr, &filt);
+        if (rc != ERH_OK) return rc;
+        rc = bm25_topk_dev(h, h->qptr, h->qtok, nb, k, filt, h->bs_ids.as<int32_t>() + (size_t)c0 * k, h->bs_sc.as<double>() + (size_t)c0 * k,
+                           h->bs_len.as<int32_t>() + c0, bytes, max_qlen, st);
+        if (rc != ERH_OK) return rc;
+    }
+    { ProfScope ps(h, st, ERH_K_BM25_MERGE, (double)n_sub * k * 12, 0);
+      HIPCHK(h, erh::launch_bm25_set_merge(h->bs_ids.as<int32_t>(), h->bs_sc.as<double>(), h->bs_len.as<int32_t>(), h->bs_tab.as<int32_t>(), B, k,
+                                           out.d_ids, out.d_sc, out.d_len, st)); }
+    h->stats.bm25_sets_merge_launches += 1;
+    return out.finish(st);
 }
 
 int erh_bm25_scores(erh_handle *h, const int32_t *q_tok, int n_tok, double *out_scores) {

@@ -225,6 +225,9 @@ struct erh_handle {
     // bw_s64: the long shape's score spans (opt_bm25_rows_ws_mb, at least one list of N rows)
     DevBuf bw_tab, bw_s64, bw_ids, bw_sc, bw_len;
     int64_t opt_bm25_rows_ws_mb = 256;
+    // erh_bm25_topk_sets (bm25_sets.hip): the sub-queries' lists [n_sub x k] that its class-column scans write and its merge reads, and
+    // bs_tab: sub_ptr int32[B + 1], one upload per call.  The scans themselves use what erh_bm25_topk uses (qpack, part_*).
+    DevBuf bs_tab, bs_ids, bs_sc, bs_len;
     bool dense_corrected = false;            // dense_check_flags changed result rows (exhaustive rounds or a group run again)
     DevBuf dir_rng;                          // {first document, last + 1} of every dir class (erh_set_doc_meta): a filtered BM25 query walks those tiles only
     int dir_rng_n = 0;
@@ -273,7 +276,8 @@ struct erh_handle {
         int64_t dense_calls = 0, dense_scan_pp5 = 0, dense_scan_pp3 = 0, dense_scan_gemv = 0, dense_scan_tile = 0,
                 dense_sample_passes = 0, dense_tile384_nomem = 0, bm25_calls = 0, hybrid_calls = 0, dense_block_groups = 0,
                 dense_grouped_launches = 0, bm25_mixed_launches = 0, dense_rows_calls = 0, dense_rows_short = 0, dense_rows_long = 0,
-                dense_group_reruns = 0, bm25_rows_calls = 0, bm25_rows_short = 0, bm25_rows_long = 0;
+                dense_group_reruns = 0, bm25_rows_calls = 0, bm25_rows_short = 0, bm25_rows_long = 0,
+                bm25_sets_calls = 0, bm25_sets_subqueries = 0, bm25_sets_merge_launches = 0;
     } stats;
     // multi-GPU exchange (erh_comm_* / erh_allgather_topk): RCCL communicator + packed send / receive rows
     void *comm = nullptr;

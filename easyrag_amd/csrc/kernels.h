@@ -378,4 +378,10 @@ hipError_t launch_bm25_rows_select(const double *S64, const int64_t *span_off, c
                                    const int32_t *list_of, const int32_t *qord, int n_q, int k, int32_t *out_ids, double *out_sc,
                                    int32_t *out_len, hipStream_t st);
 
+// ---- bm25_sets.hip: set filters on the sparse route (erh_bm25_topk_sets) ----------------------------------------------------------------
+// out row b = the canonical top k of the union of the sub-lists sub_ptr[b] .. sub_ptr[b + 1] of [rows x k] (each canonical, sub_len entries,
+// disjoint document sets), padded with id -1 / score 0; k <= 1024; no sub-list: length 0
+hipError_t launch_bm25_set_merge(const int32_t *sub_ids, const double *sub_sc, const int32_t *sub_len, const int32_t *sub_ptr, int B, int k,
+                                 int32_t *out_ids, double *out_sc, int32_t *out_len, hipStream_t st);
+
 }  // namespace erh

@@ -423,6 +423,20 @@ class RetrievalEngine:
                                                  self._stream(stream)))
         return ids, sc, ln
 
+    def bm25_topk_sets(self, q_indptr, q_tok, k: int, sets, device_out: bool = False, stream=None, slot: Optional[int] = None):
+        """BM25 top-k where query b may see the documents whose class is in sets[b] (erh_bm25_topk_sets): a sequence of class ids, None
+        for unfiltered; an empty sequence returns nothing.  Only documents with a score > 0 are returned, as everywhere on this route;
+        (score desc, document id asc).  device_out: results are final after sync() -- no dense_check() is needed."""
+        self._select(slot)
+        q_indptr = _np(q_indptr, np.int32)
+        q_tok = _np(q_tok, np.int32)
+        B = q_indptr.shape[0] - 1
+        ptr, cls = self.sets_to_csr(sets, B)
+        ids, sc, ln = self._outs(B, k, device_out)
+        self._check(self._lib.erh_bm25_topk_sets(self._h, _ptr(q_indptr), _ptr(q_tok), B, int(k), _ptr(ptr), _ptr(cls),
+                                                 _ptr(ids), _ptr(sc), _ptr(ln), 1 if device_out else 0, self._stream(stream)))
+        return ids, sc, ln
+
     def bm25_scores(self, q_tok, slot: Optional[int] = None) -> np.ndarray:
         self._select(slot)
         assert self.bm25 is not None
@@ -642,6 +656,7 @@ class RetrievalEngine:
                   "dense_exhaustive_queries", "bm25_redo_segments", "dense_block_groups", "dense_grouped_launches", "bm25_mixed_launches",
                   "dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches", "dense_group_reruns",
                   "bm25_rows_calls", "bm25_rows_short_launches", "bm25_rows_long_launches",
+                  "bm25_sets_calls", "bm25_sets_subqueries", "bm25_sets_merge_launches",
                   "hybrid_lazy_queries", "dense_rescored_rows_last_call")
 
     def stat(self, name: str) -> int:

@@ -255,6 +255,8 @@ def _holds(node, meta: Dict[str, Any]) -> bool:
         _, must, should, must_not = node
         return (all(_holds(x, meta) for x in must) and (not should or any(_holds(x, meta) for x in should))
                 and not any(_holds(x, meta) for x in must_not))
+    if op == "both":                                               # a filter_dict AND a compiled filter (_both): the class column's
+        return all(meta.get(k) == v for k, v in node[1]) and _holds(node[2], meta)   # equality (an absent key equals None), then the tree
     key = node[1]
     if key not in meta:
         return False                                               # a row without the key fails every condition on it
@@ -309,6 +311,21 @@ def _filter_spec(filters):
     if not keys:                                                   # nested empty filters only: a constant
         return None if _holds(node, {}) else _MATCH_NOTHING
     return _SetFilter(node, keys)
+
+
+def _both(d: Optional[Dict[str, Any]], f):
+    """The sparse route's two filters of one query as ONE spec: the rows that pass the filter_dict `d` AND the compiled `filters` entry `f`
+    (None, a dict or a _SetFilter).  Two dicts merge (contradicting values match nothing); a dict beside a set filter becomes a set filter
+    over the union of their keys, so that its class set is the intersection of the two filters' class sets in the column over those keys."""
+    if not d:
+        return f
+    if not f:
+        return d
+    if isinstance(f, dict):
+        if any(k in d and d[k] != v for k, v in f.items()):
+            return _MATCH_NOTHING
+        return {**d, **f}
+    return _SetFilter(("both", tuple(sorted(d.items(), key=repr)), f.node), set(d) | set(f.keys))
 
 
 def _filter_to_dict(filters) -> Optional[Dict[str, Any]]:
@@ -1025,6 +1042,7 @@ class BM25Retriever(_RetrieverBase):
                                          compute_payload=not payload_on_device)
             self.engine.set_bm25(self.bm25, payload_on_device=payload_on_device, slot=self._slot)
         self.filter_dict = None
+        self.filters = None                    # a Qdrant-style Filter for every query (retrieve_batch's `filters`); not the reference's knob
         self._init_base(callback_manager=callback_manager, object_map=object_map, objects=objects, verbose=verbose)
 
     @staticmethod
@@ -1113,43 +1131,93 @@ class BM25Retriever(_RetrieverBase):
         return self.retrieve_batch([query_bundle.query_str])[0]
 
     def _resolve_rows(self, dicts, rows, B: int):
-        """Per query the rows it may rank (None: it runs through the class-column call) and the filters left for that call.  A query with
-        rows AND a filter_dict keeps the rows that pass the filter: a host lookup in the class column over the filter's keys."""
+        """Per query the rows it may rank (None: it runs through the class-column / class-set calls) and the filters left for those calls
+        (a dict or a _SetFilter each).  A query with rows AND a filter keeps the rows that pass the filter: a host lookup in the class
+        column over the filter's keys.  A filter over more distinct value tuples than a class column holds becomes the rows it matches
+        (_FilteredCorpus.rows_matching), as on the dense route."""
         rows_q = _per_query_rows(rows, B, len(self._nodes))
         dicts = list(dicts)
+        corpus = self._corpus_state
         for b in range(B):
-            if rows_q[b] is not None and dicts[b]:
-                c = self._corpus_state.filter_class(dicts[b])          # (32767: no document carries these values)
+            sp = dicts[b]
+            if not sp:
+                continue
+            keys = _spec_keys(sp)
+            if keys and corpus.too_many_values(keys):
+                allowed = corpus.rows_matching(sp)
+                rows_q[b] = allowed if rows_q[b] is None else np.intersect1d(rows_q[b], allowed, assume_unique=True)
+                dicts[b] = None
+            elif rows_q[b] is not None:
+                c = corpus.plan([sp])[0]       # -1 everything, a class (32767: no document carries these values), a list of classes
                 r = rows_q[b]
-                rows_q[b], dicts[b] = r[self._corpus_state._classes.ids[r] == c], None
+                if isinstance(c, list):
+                    r = r[np.isin(corpus._classes.ids[r], np.asarray(c, np.int64))] if c else r[:0]
+                elif c != -1:
+                    r = r[corpus._classes.ids[r] == c]
+                rows_q[b], dicts[b] = r, None
         return rows_q, dicts
 
-    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, rows=None) -> List[List[NodeWithScore]]:
+    def _host_mask(self, spec, rows: Optional[np.ndarray]):
+        """The host walk's arguments for one query: (filter_dict, rows).  A dict stays the walk's own equality test; a set filter
+        becomes the rows it matches (with `rows`: those of them)."""
+        if not isinstance(spec, _SetFilter):
+            return spec, rows
+        allowed = self._corpus_state.rows_matching(spec)
+        return None, allowed if rows is None else np.intersect1d(rows, allowed, assume_unique=True)
+
+    def _topk_planned(self, tok: Sequence[np.ndarray], plan: List[Any]):
+        """One key-set group after corpus.plan: queries whose filter matches no row get nothing (no scan); a group without a set of two
+        or more classes is today's class-column call, any other erh_bm25_topk_sets."""
+        B, k = len(plan), self._similarity_top_k
+        if any(isinstance(c, list) and len(c) > 1 for c in plan):
+            qi, qt = queries_to_csr(tok)
+            return self.engine.bm25_topk_sets(qi, qt, k, [None if c == -1 else (c if isinstance(c, list) else [c]) for c in plan],
+                                              slot=self._slot)
+        ids, sc, ln = np.full((B, k), -1, np.int32), np.zeros((B, k), np.float64), np.zeros(B, np.int32)
+        live = [b for b in range(B) if not isinstance(plan[b], list)]
+        if live:
+            col = np.asarray([plan[b] for b in live], np.int16)
+            qi, qt = queries_to_csr([tok[b] for b in live])
+            ids[live], sc[live], ln[live] = self.engine.bm25_topk(qi, qt, k, slot=self._slot, filter_dir=col if np.any(col >= 0) else None)
+        return ids, sc, ln
+
+    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, rows=None, filters=_UNSET) -> List[List[NodeWithScore]]:
         """get_scores + filter for a whole batch, fused on the GPU (no score vector leaves the chip).  `filter_dicts`
         (default: the `filter_dict` attribute, for every query) may be a list parallel to `queries`: one dict / None each.
+        `filters` (default: the `filters` attribute): a Qdrant-style Filter -- MatchValue / MatchAny / MatchExcept / Range, must / should /
+        must_not with nesting, compiled like the dense route's (unsupported elements raise TypeError before any engine call) -- or a list
+        of them parallel to `queries`.  A query with a filter_dict and a filter sees the rows that pass BOTH.  Every class allowed: the
+        unfiltered call; one class: the class-column call; none: an empty list without a call; two or more: erh_bm25_topk_sets.
         `rows`: restrict queries to explicit node positions -- one id array for every query, or a list parallel to the queries whose
         entries are an id array or None (HipVectorStore.query_batch's argument, normalised the same way).  Such a query ranks exactly
-        those rows by the corpus index's BM25 (erh_bm25_topk_rows; with a filter_dict as well: the rows that also pass it), the others
+        those rows by the corpus index's BM25 (erh_bm25_topk_rows; with a filter as well: the rows that also pass it), the others
         run as without the argument, and the two parts are scattered into one result."""
         B = len(queries)
         if B == 0:
             return []
         dicts = _per_query(self.filter_dict if filter_dicts is _UNSET else filter_dicts, B, lambda v: dict(v) if v else None)
+        fl = self.filters if filters is _UNSET else filters
+        if fl is not None:
+            dicts = [_both(d, f) for d, f in zip(dicts, _per_query(fl, B, _spec_cache()))]
         tok = [self._query_ids(q) for q in queries]
         k = self._similarity_top_k
         rows_q, dicts = self._resolve_rows(dicts, rows, B)
         if not 1 <= k <= BM25_DEVICE_MAX_K:
             # outside the fused kernels' range (erh_bm25_topk: 1 <= k <= 1024) the reference's answer is still defined: the
-            # score vector plus the host filter (restricted to the rows) give it exactly
-            return [self._filter_one(self._cast(self.engine.bm25_scores(t, slot=self._slot)), d, k, rows=r)
-                    for t, d, r in zip(tok, dicts, rows_q)]
+            # score vector plus the host filter (restricted to the rows; a set filter as the rows it matches) give it exactly
+            masks = [self._host_mask(d, r) for d, r in zip(dicts, rows_q)]
+            return [self._filter_one(self._cast(self.engine.bm25_scores(t, slot=self._slot)), fd, k, rows=keep)
+                    for t, (fd, keep) in zip(tok, masks)]
         out: List[List[NodeWithScore]] = [[] for _ in range(B)]
         rest = [b for b in range(B) if rows_q[b] is None]
         for g in _by_key_set([dicts[b] for b in rest]):
             g = [rest[j] for j in g]
-            qi, qt = queries_to_csr([tok[b] for b in g])
-            ids, sc, ln = self.engine.bm25_topk(qi, qt, self._similarity_top_k, slot=self._slot,
-                                                filter_dir=self._corpus_state.filter_column([dicts[b] for b in g]))
+            if any(isinstance(dicts[b], _SetFilter) for b in g):
+                ids, sc, ln = self._topk_planned([tok[b] for b in g], self._corpus_state.plan([dicts[b] for b in g]))
+            else:
+                qi, qt = queries_to_csr([tok[b] for b in g])
+                ids, sc, ln = self.engine.bm25_topk(qi, qt, self._similarity_top_k, slot=self._slot,
+                                                    filter_dir=self._corpus_state.filter_column([dicts[b] for b in g]))
             for j, b in enumerate(g):
                 out[b] = [NodeWithScore(node=self._nodes[i], score=float(s)) for i, s in zip(ids[j, :ln[j]], sc[j, :ln[j]])]
         with_rows = [b for b in range(B) if rows_q[b] is not None]
@@ -1330,7 +1398,7 @@ class HybridRetriever(_RetrieverBase):
         return self.retrieve_batch([query_bundle.query_str])[0]
 
     def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, filters=_UNSET, rows=None,
-                       sparse_rows=None) -> List[List[NodeWithScore]]:
+                       sparse_rows=None, sparse_filters=_UNSET) -> List[List[NodeWithScore]]:
         """`_aretrieve` for a batch of query strings.  Without the keyword arguments the `filter_dict` / `filters`
         attributes apply to every query and are pushed into the child retrievers as the reference does
         (retrievers.py:278,283).  `filter_dicts` (sparse route) / `filters` (dense route) may instead be lists parallel to
@@ -1338,7 +1406,11 @@ class HybridRetriever(_RetrieverBase):
         batch of its questions needs one filter per query; the child retrievers' attributes are left alone then.
         `rows` restricts the DENSE route (QdrantRetriever.retrieve_batch's argument); the sparse route keeps its filter_dict.
         `sparse_rows` restricts the SPARSE route (BM25Retriever.retrieve_batch's `rows`); the same object passed as both holds the
-        fused call to one id set: RRF then runs on two lists drawn from the same population."""
+        fused call to one id set: RRF then runs on two lists drawn from the same population.
+        `sparse_filters` (not given: the sparse route gets its filter_dict only, as in the reference) hands the SPARSE route a Qdrant-style
+        Filter as well (BM25Retriever.retrieve_batch's `filters`; one, or a list parallel to `queries`); the same object passed as
+        `filters` and `sparse_filters` holds both routes to one population -- erh_bm25_topk_sets and erh_dense_topk_sets into device
+        buffers, then the RRF kernel."""
         sp, de = self.sparse_retriever, self.dense_retriever
         B = len(queries)
         if B == 0:
@@ -1346,6 +1418,8 @@ class HybridRetriever(_RetrieverBase):
         fs = self.filter_dict if filter_dicts is _UNSET else filter_dicts
         fdn = self.filters if filters is _UNSET else filters
         s_kw = {} if sparse_rows is None else {"rows": sparse_rows}
+        if sparse_filters is not _UNSET:
+            s_kw["filters"] = sparse_filters
         if self.retrieval_type != 1:
             if filter_dicts is _UNSET:
                 sp.filter_dict = self.filter_dict
@@ -1358,9 +1432,16 @@ class HybridRetriever(_RetrieverBase):
                 return de.retrieve_batch(queries, filters=fdn, rows=rows)
         # filter_dict restricts the sparse route only, filters the dense route only (retrievers.py:278,283)
         d_sparse = _per_query(fs, B, lambda v: dict(v) if v else None)
-        d_dense = _per_query(fdn, B, _spec_cache())
+        spec = _spec_cache()                           # (one cache: the same object on both routes compiles once)
+        d_dense = _per_query(fdn, B, spec)
+        if sparse_filters is not _UNSET and sparse_filters is not None:
+            d_sparse = [_both(d, f) for d, f in zip(d_sparse, _per_query(sparse_filters, B, spec))]
         key_sets = {_spec_keys(fd) for fd in d_sparse + d_dense if _spec_keys(fd)}
-        if not self._fused_possible() or len(key_sets) > 1 or not self._fused_sizes():
+        s_sets = any(isinstance(fd, _SetFilter) for fd in d_sparse)
+        # a sparse filter over more distinct values than a class column numbers runs through the sparse route's own rows entry
+        s_many = self._fused_possible() and any(
+            _spec_keys(fd) and sp._corpus_state.too_many_values(_spec_keys(fd)) for fd in d_sparse if fd)
+        if not self._fused_possible() or len(key_sets) > 1 or not self._fused_sizes() or (s_many and sparse_rows is None):
             # (outside erh_hybrid_topk's sizes the routes run on their own: each one falls back or names its limit)
             sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs, **s_kw), de.retrieve_batch(queries, filters=fdn, rows=rows)
             return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
@@ -1375,11 +1456,13 @@ class HybridRetriever(_RetrieverBase):
             return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
         if rows is not None or any(sp and _spec_keys(sp) and vs.corpus.too_many_values(_spec_keys(sp)) for sp in d_dense):
             rows_q, _ = vs._resolve_rows(d_dense, rows, B, _lib.ERH_DENSE_EXACT)
-            if any(r is None for r in rows_q):         # a batch that mixes rows and non-rows dense queries: the routes on their own + RRF
-                sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs), de.retrieve_batch(queries, filters=fdn, rows=rows)
+            if s_sets or any(r is None for r in rows_q):
+                # a batch that mixes rows and non-rows dense queries, or a set filter on the sparse route beside dense rows: the routes
+                # on their own + RRF
+                sparse, dense = sp.retrieve_batch(queries, filter_dicts=fs, **s_kw), de.retrieve_batch(queries, filters=fdn, rows=rows)
                 return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
             return self._retrieve_rows(queries, d_sparse, rows_q)
-        if any(isinstance(fd, _SetFilter) for fd in d_dense):
+        if s_sets or any(isinstance(fd, _SetFilter) for fd in d_dense):
             return self._retrieve_sets(queries, d_sparse, d_dense)
         # both routes share one engine: BM25 -> dense -> RRF([sparse, dense]) in a single device pipeline, one class column
         # per route over the shared key set (a query's two filters may still differ, or one of them be absent)
@@ -1395,17 +1478,27 @@ class HybridRetriever(_RetrieverBase):
                 for b in range(B)]
 
     def _retrieve_sets(self, queries: Sequence[str], d_sparse, d_dense) -> List[List[NodeWithScore]]:
-        """retrieval_type 3 with a set-valued dense filter: every step on the device, no host round trip between them -- BM25
-        top-k (class column of filter_dict) and erh_dense_topk_sets into device buffers, erh_dense_check (sub-queries answered
-        by the exhaustive path merged again), then the RRF kernel over the two device lists."""
+        """retrieval_type 3 with a set-valued filter on either route: every step on the device, no host round trip between them -- BM25
+        top-k (class column of filter_dict; with a set filter on the sparse route, `sparse_filters`: erh_bm25_topk_sets) and
+        erh_dense_topk_sets into device buffers, erh_dense_check (sub-queries answered by the exhaustive path merged again), then the
+        RRF kernel over the two device lists."""
         sp, de = self.sparse_retriever, self.dense_retriever
         eng, cstate = sp.engine, sp._corpus_state
         B = len(queries)
-        filt_s = cstate.filter_column(d_sparse)
-        plan = cstate.plan(d_dense)                    # (same key set as filt_s: the caller checked; the column stays put)
+        s_sets = any(isinstance(fd, _SetFilter) for fd in d_sparse)
+        if s_sets:
+            plan_s = cstate.plan(d_sparse)
+        else:
+            filt_s = cstate.filter_column(d_sparse)
+        plan = cstate.plan(d_dense)                    # (same key set as the sparse route's: the caller checked; the column stays put)
         qi, qt = queries_to_csr([sp._query_ids(q) for q in queries])
         embs = _unit_f16(np.asarray([de._embed_model.get_query_embedding(q) for q in queries], dtype=np.float32))
-        sids, _, sln = eng.bm25_topk(qi, qt, sp._similarity_top_k, filter_dir=filt_s, device_out=True, slot=sp._slot)
+        if s_sets:
+            sids, _, sln = eng.bm25_topk_sets(qi, qt, sp._similarity_top_k,
+                                              [None if c == -1 else (c if isinstance(c, list) else [c]) for c in plan_s],
+                                              device_out=True, slot=sp._slot)
+        else:
+            sids, _, sln = eng.bm25_topk(qi, qt, sp._similarity_top_k, filter_dir=filt_s, device_out=True, slot=sp._slot)
         dids, _, dln = eng.dense_topk_sets(embs, de._similarity_top_k,
                                            [None if c == -1 else (c if isinstance(c, list) else [c]) for c in plan], device_out=True)
         eng.dense_check()

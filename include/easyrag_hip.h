@@ -38,6 +38,7 @@
  *   erh_bm25_topk        BM25Retriever._retrieve = get_scores + filter (retrievers.py:191-220)
  *   erh_bm25_topk_rows   the same where the filter's keep mask is an explicit id set per query (retrievers.py:128-151, 191-210): every listed
  *                        row scored exactly, no scan of the postings
+ *   erh_bm25_topk_sets   the same where the keep mask is a set of classes per query (retrievers.py:128-151, 191-210)
  *   erh_rrf              HybridRetriever.reciprocal_rank_fusion (retrievers.py:256-274)
  *   erh_fusion           HybridRetriever.fusion (retrievers.py:239-253)
  *   erh_hybrid_topk      HybridRetriever._aretrieve, retrieval_type == 3 (retrievers.py:276-291)
@@ -280,6 +281,29 @@ int erh_bm25_topk(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, 
  * chunks of queries, one behind the other on the stream. */
 int erh_bm25_topk_rows(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
                        int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
+                       int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
+
+/* BM25 top-k where each query may see a SET of classes: what BM25Retriever.get_scores + .filter return
+ * (src/easyrag/custom/retrievers.py:128-151, 191-210) when the keep mask is "the document's class is one of these" -- a Qdrant payload
+ * filter with MatchAny / MatchExcept / should / must_not / Range evaluated on the host over the class column's distinct values
+ * (easyrag_amd/retrievers.py) -- and the sparse twin of erh_dense_topk_sets.  Acts on the slot chosen by erh_bm25_select.
+ *   Queries as for erh_bm25_topk (host CSR of term ids in [0, V); an empty query gives out_len[b] = 0).  Sets as for erh_dense_topk_sets:
+ *   set_ptr int32[B+1], set_cls int16[set_ptr[B]] (host CSR): query b sees the documents whose class (erh_set_doc_meta dir_id) is one of
+ *   set_cls[set_ptr[b] .. set_ptr[b+1]).  The set {-1} alone = unfiltered; an empty set = out_len[b] = 0 without a scan; 32767 (or any class
+ *   no document carries) contributes nothing.  Classes within a set must be distinct and >= 0.
+ *   Errors: a malformed CSR (queries or sets), a term id outside [0, V) or a null pointer: ERH_ERR_INVALID; k outside [1, 1024]:
+ *   ERH_ERR_UNSUPPORTED; no index in the slot, or a set other than {-1} while no class column covers the slot's N documents: ERH_ERR_STATE;
+ *   work space that cannot be allocated: ERH_ERR_NOMEM.  All of it is checked on the host before anything is enqueued (outputs untouched).
+ * Result for query b: its documents whose class is in the set and whose score is > 0 (retrievers.py:195-196) under (score descending,
+ * document id ascending), the first k; scores as float64 (float32 sums widened exactly); padded with id -1, score 0; out_len[b] = min(k,
+ * number of positive documents in the set).  Every (query, allowed class) pair runs as a sub-query of ordinary class-column batches of
+ * erh_bm25_topk's scan (chunks of 8192 sub-queries, one behind the other on the stream; with option bm25_dir_range a sub-query walks the
+ * posting tiles of its class only), and one merge kernel takes the top k of each query's sub-lists -- exact: every document has one class,
+ * and the score > 0 cut is per document.
+ * Host outputs are final on return, device outputs after erh_sync.  The call sets no flag words (erh_dense_check has nothing to do on its
+ * account); it counts once in bm25_calls. */
+int erh_bm25_topk_sets(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
+                       const int32_t *set_ptr, const int16_t *set_cls,
                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
 
 /* Dense score vector of one query (host int32[n_tok]) over all N documents: float64[N] on the host
@@ -549,6 +573,8 @@ int erh_dense_exhaustive_count(erh_handle *h, int32_t *count);
  *   bm25_rows_calls                                    erh_bm25_topk_rows calls
  *   bm25_rows_short_launches / bm25_rows_long_launches    its launches of the short shape (one workgroup per query, lists of at most 2048 rows) /
  *                                                      of the long shape (one score + select pair per chunk of queries)
+ *   bm25_sets_calls                                    erh_bm25_topk_sets calls (each also counts once in bm25_calls)
+ *   bm25_sets_subqueries / bm25_sets_merge_launches    its (query, allowed class) sub-queries, summed over calls / its merge launches (one per call)
  *   bm25_mixed_launches                                BM25 scans launched with both bodies (bm25_mixed: a batch with queries longer than bm25_long_tokens)
  *   bm25_redo_segments                                 (query, segment) pairs the fixed-point scan handed to the exact block scan (device counter)
  * Reading a device counter synchronises the device.  Unknown name: ERH_ERR_INVALID. */
