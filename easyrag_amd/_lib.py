@@ -86,6 +86,7 @@ SIGNATURES = {
     "erh_dense_seed_rank": (_i32, [_i32, _i64, _i64]),
     "erh_debug_dense_scores": (_i32, [_vp, _vp, _i32, _i64, _i32, _i32, _vp]),
     "erh_debug_dense_query_state": (_i32, [_vp, _vp, _vp, _vp, _i32]),
+    "erh_debug_rows_class_sets": (_i32, [_i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32]),
     "erh_vocab_create": (_i32, [C.POINTER(_vp)]),
     "erh_vocab_destroy": (_i32, [_vp]),
     "erh_vocab_size": (_i64, [_vp]),

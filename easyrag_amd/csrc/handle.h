@@ -228,6 +228,27 @@ struct erh_handle {
     // erh_bm25_topk_sets (bm25_sets.hip): the sub-queries' lists [n_sub x k] that its class-column scans write and its merge reads, and
     // bs_tab: sub_ptr int32[B + 1], one upload per call.  The scans themselves use what erh_bm25_topk uses (qpack, part_*).
     DevBuf bs_tab, bs_ids, bs_sc, bs_len;
+    // Scan route of the rows entries (rows_classes.hip, DESIGN K11): the long lists of a call numbered as a CALL-LOCAL class column that the
+    // sets pipelines run on in place of the handle's own.  Buffers of the rows routes, one set per route (the two corpora may differ in size);
+    // the next routed call of the route reuses them in stream order.  sig: uint64[N] membership words; cls: int16[N] the column; pos: its
+    // copy by stored position (dense, built by the pipeline on demand); table: header | cells | open-addressing table; rng: the cells' row
+    // ranges as bm25_dir_range reads them.
+    struct RowsClasses {
+        DevBuf sig, cls, pos, table, rng;
+        DevBuf keep;                                                   // the call's uploaded row ids, kept across a hand-back to the row-by-row shapes
+        std::vector<char> cells_host;                                  // header + cells as read back
+        std::vector<int32_t> rng_host;
+    } rwc, bwc;
+    int opt_dense_rows_scan = 1, opt_bm25_rows_scan = 1;               // 1 = by the work rule, 0 = never (parity arm), 2 = every eligible list
+    int64_t opt_dense_rows_scan_min_rows = 131072, opt_bm25_rows_scan_min_rows = 131072;   // shorter lists never route
+    // The work rule's constants (measured at 1M rows, d = 1024: profiles/rows_scan_timing.json).  Dense: one (group of 8 queries, listed row)
+    // pair of the long shape costs what dense_rows_scan_gain (row, query column) pairs of the scan cost (1.8 ns against 2.6 ps), a scan
+    // narrower than dense_route_ridge columns counted as the ridge, and a sub-query on a cell too small to seed a threshold counted as
+    // dense_rows_scan_small_cell sub-queries (33 us against 2.6 us).  BM25: one (query, listed row) pair costs what bm25_rows_scan_gain
+    // (sub-query, row) pairs of the scan cost, and every cell counts as bm25_rows_scan_floor sub-queries more.
+    int64_t opt_dense_rows_scan_gain = 700, opt_dense_rows_scan_small_cell = 13, opt_bm25_rows_scan_gain = 80, opt_bm25_rows_scan_floor = 20;
+    bool check_pending = false;              // a device-output scan-route dense / fused call has not been through erh_dense_check yet: its work
+                                             // space (Q16, flags, cand, s_*, r_*) is live, and a rows call keeps to its own shapes
     bool dense_corrected = false;            // dense_check_flags changed result rows (exhaustive rounds or a group run again)
     DevBuf dir_rng;                          // {first document, last + 1} of every dir class (erh_set_doc_meta): a filtered BM25 query walks those tiles only
     int dir_rng_n = 0;
@@ -277,7 +298,9 @@ struct erh_handle {
                 dense_sample_passes = 0, dense_tile384_nomem = 0, bm25_calls = 0, hybrid_calls = 0, dense_block_groups = 0,
                 dense_grouped_launches = 0, bm25_mixed_launches = 0, dense_rows_calls = 0, dense_rows_short = 0, dense_rows_long = 0,
                 dense_group_reruns = 0, bm25_rows_calls = 0, bm25_rows_short = 0, bm25_rows_long = 0,
-                bm25_sets_calls = 0, bm25_sets_subqueries = 0, bm25_sets_merge_launches = 0;
+                bm25_sets_calls = 0, bm25_sets_subqueries = 0, bm25_sets_merge_launches = 0,
+                dense_rows_scan_calls = 0, dense_rows_scan_subqueries = 0, bm25_rows_scan_calls = 0, bm25_rows_scan_subqueries = 0,
+                dense_block_builds = 0;
     } stats;
     // multi-GPU exchange (erh_comm_* / erh_allgather_topk): RCCL communicator + packed send / receive rows
     void *comm = nullptr;
@@ -355,6 +378,7 @@ struct erh_handle {
     void forget_dense_call() {               // nothing of the last dense call is left for erh_dense_check / erh_debug_dense_query_state to read
         last = LastDense(); qstate = QueryState();
         routed.done = routed.pending = sets.on = false;
+        check_pending = false;
     }
 
     int fail(int code, const char *what, hipError_t e = hipSuccess) {

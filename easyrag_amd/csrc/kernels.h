@@ -384,4 +384,21 @@ hipError_t launch_bm25_rows_select(const double *S64, const int64_t *span_off, c
 hipError_t launch_bm25_set_merge(const int32_t *sub_ids, const double *sub_sc, const int32_t *sub_len, const int32_t *sub_ptr, int B, int k,
                                  int32_t *out_ids, double *out_sc, int32_t *out_len, hipStream_t st);
 
+// ---- rows_classes.hip: the long lists of a rows call as a call-local class column (DESIGN K11) -----------------------------------------
+constexpr int kRowsClassLists = 64;        // routed lists of one call: one bit of a row's signature word each
+constexpr int kRowsClassMax = 32766;       // distinct signatures (cells) a call-local int16 column can number (32767 = matches nothing)
+// One cell: the rows with the same membership signature (bit l: the row is in routed list l); rows lie in [lo, hi)
+struct ErhRowsCell {
+    uint64_t sig;
+    int32_t cnt, lo, hi, pad;
+};
+static_assert(sizeof(ErhRowsCell) == 24, "ErhRowsCell layout");
+int rows_classes_slots(int64_t max_cells);                 // open-addressing slots for at most max_cells cells (a power of two)
+size_t rows_classes_table_bytes(int slots, int max_cells); // header (16 bytes: cells, overflow) | max_cells cells | the table itself
+// routed: {first entry, length} int64 pairs of the n_routed lists (device), entries in `rows`; sig uint64[N] and `table` are cleared here.
+// Writes cls int16[N] (cell number, -1: in no routed list) and the header + cells at the front of `table` (what the host reads back:
+// 16 + 24 * min(cells, max_cells) bytes).  Cell numbers are handed out in arrival order: they differ from run to run, nothing else does.
+hipError_t launch_rows_classes(const int32_t *rows, const int64_t *routed, int n_routed, int64_t max_len, int64_t N, int slots, int max_cells,
+                               unsigned long long *sig, void *table, int16_t *cls, hipStream_t st);
+
 }  // namespace erh

@@ -596,6 +596,7 @@ static int routed_group_scatter(erh_handle *h, const erh_handle::RoutedGroup &g,
 // for the large one, not for a second copy of everything), + kDensePadRows zero rows.
 static int ensure_dense_blocks(erh_handle *h, hipStream_t st) {
     if (h->blocks.valid) return ERH_OK;
+    h->stats.dense_block_builds += 1;
     const int nc = (int)h->dir_cnt_h.size();
     const int d = h->d;
     h->blocks.lo.assign(nc, 0); h->blocks.n.assign(nc, 0); h->blocks.mul.assign(nc, 1); h->blocks.inv.assign(nc, 1);

@@ -657,6 +657,8 @@ class RetrievalEngine:
                   "dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches", "dense_group_reruns",
                   "bm25_rows_calls", "bm25_rows_short_launches", "bm25_rows_long_launches",
                   "bm25_sets_calls", "bm25_sets_subqueries", "bm25_sets_merge_launches",
+                  "dense_rows_scan_calls", "dense_rows_scan_subqueries", "bm25_rows_scan_calls", "bm25_rows_scan_subqueries",
+                  "dense_block_builds",
                   "hybrid_lazy_queries", "dense_rescored_rows_last_call")
 
     def stat(self, name: str) -> int:

@@ -251,7 +251,25 @@ int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_devi
  * erh_dense_check, a check behind it does nothing on its account (it still finishes an earlier dense call that waits for one -- a rows call
  * may sit between such a call and its check), and erh_dense_diag / erh_dense_exhaustive_count, which describe scan-route calls, count no query of it.
  * Option dense_rows_ws_mb (256): score work space of lists longer than 2048 rows, at least one list of N rows; a call that needs more runs in
- * chunks of queries. */
+ * chunks of queries.
+ * LONG LISTS THROUGH THE SCAN (options dense_rows_scan, dense_rows_scan_min_rows, dense_rows_scan_gain below).  Scoring every listed row costs
+ * (queries x listed rows); the pruned scan costs about the same whatever the filter.  So the lists of a call that are long enough, and whose
+ * row-by-row work exceeds the scan's, are numbered as a CALL-LOCAL class column -- overlapping lists cut the rows into cells of equal
+ * membership, each list is a set of cells -- and their queries run as one set-filtered batch of erh_dense_topk_sets' pipeline on that column,
+ * installed in place of the handle's own class state for the call and restored before it returns (error paths included).  Results are
+ * bit-identical to the row-by-row shapes: the same pinned-order fp64 score, (score descending, row id ascending).  Validation, padding,
+ * out_len and status codes are unchanged; queries on short lists, on long lists that stay, and without a list keep their shapes in the same
+ * call.  The call keeps its contract -- no erh_dense_check, host outputs final on return, device outputs after erh_sync: the routed batch is
+ * checked inside the call (one stream synchronisation).  Two additions to that contract:
+ *   - after a call that took the scan route, erh_dense_diag / erh_dense_exhaustive_count report over ITS sub-queries ((query, cell) pairs),
+ *     as after erh_dense_topk_sets, and a later erh_dense_check has nothing left to do;
+ *   - while a device-output erh_dense_topk / erh_dense_topk_sets / erh_hybrid_topk call still waits for its erh_dense_check, a rows call
+ *     does not take the scan route (it would overwrite that call's work space): it runs on the row-by-row shapes, as before.
+ * The same fall-back, for the whole call and without error, when it names more than 64 routable lists or they cut the rows into more than
+ * 32766 cells (the classification stops at the first cell too many: it costs a few passes over N words, never a walk of its table per row;
+ * the row ids stay on the device for the row-by-row pass and are not validated or uploaded again).  A routed call counts once in dense_rows_calls and dense_rows_scan_calls, not in dense_rows_long_launches and not in
+ * dense_calls; its scans move the dense_scan_*_launches / dense_sample_passes counters and dense_candidates_last_call /
+ * dense_rescored_rows_last_call like any scan-route call. */
 int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q, int B, int k,
                         int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
                         int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
@@ -278,7 +296,18 @@ int erh_bm25_topk(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, 
  * account) and keeps to buffers of its own: enqueued behind a device-output erh_bm25_topk / erh_dense_topk / erh_dense_topk_rows on the same
  * stream it leaves that call's results intact.
  * Option bm25_rows_ws_mb (256): score work space of lists longer than 2048 rows, at least one list of N rows; a call that needs more runs in
- * chunks of queries, one behind the other on the stream. */
+ * chunks of queries, one behind the other on the stream.
+ * LONG LISTS THROUGH THE SCAN (options bm25_rows_scan, bm25_rows_scan_min_rows, bm25_rows_scan_gain, bm25_rows_scan_floor below): as on the
+ * dense route (erh_dense_topk_rows), the lists of a call that are long enough, and whose (queries x listed rows) work exceeds the scan's, are
+ * numbered as a call-local class column over the slot's documents and their queries run as one set-filtered batch of erh_bm25_topk_sets'
+ * pipeline on that column, installed for the call and restored before it returns.  Results are bit-identical to the row-by-row shapes
+ * (library-order sums, score > 0 only, (score descending, row id ascending)); validation, padding, out_len and status codes are unchanged.
+ * One addition to the contract: a call that takes the scan route SHARES THE SCAN'S WORK SPACE (the query upload and partial lists of
+ * erh_bm25_topk, the sub-lists of erh_bm25_topk_sets), so like two erh_bm25_topk calls it must be ordered with the handle's other scan
+ * calls -- enqueued behind a device-output erh_bm25_topk on the same stream it is; on another stream the caller orders them.  More than 64
+ * routable lists, or more than 32766 cells: the whole call on the row-by-row shapes, without error.  A routed call counts once in
+ * bm25_rows_calls and bm25_rows_scan_calls, not in bm25_rows_long_launches, bm25_calls or the bm25_sets_* counters; its scans move
+ * bm25_mixed_launches and bm25_redo_segments like any scan. */
 int erh_bm25_topk_rows(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
                        int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
@@ -488,6 +517,22 @@ int erh_reset_kernel_time(erh_handle *h);
  *   dense_group_sample (1)  grouped launch: thresholds from a sample pass of the scan kernel per view (where every view of the batch can give
  *                         one) instead of store kernel + seed scores + seed select; 0: always the latter.  Same results
  *   dense_route_ridge (160) query columns below which a dense scan is HBM-bound on this chip (the route decision's only constant)
+ *   dense_rows_scan (1), bm25_rows_scan (1)   erh_dense_topk_rows / erh_bm25_topk_rows: long lists through the scan on a call-local class
+ *                         column.  1 = where the work rule says so, 0 = never (the row-by-row shapes: a parity arm), 2 = every list of at
+ *                         least *_rows_scan_min_rows rows (tests).  Same results
+ *   dense_rows_scan_min_rows (131072), bm25_rows_scan_min_rows (131072)   lists shorter than this (or of at most 2048 rows) never take
+ *                         the scan route, whatever the rule says
+ *   dense_rows_scan_gain (700), dense_rows_scan_small_cell (13)   the dense rule: route iff  gain x sum over the lists of
+ *                         ceil(queries / 8) x rows  >  N x max(sub-queries, dense_route_ridge) -- today's long shape loads a list once per
+ *                         group of 8 queries (1.8 ns per row and group at d = 1024); a scan column costs 2.6 ps per row, and a scan narrower
+ *                         than the ridge costs like the ridge.  Once the cells are known, a sub-query on a cell with fewer than k N / dense_n0
+ *                         rows (the seed prefix holds fewer than k of them: nothing to prune with) counts as small_cell sub-queries.
+ *                         (One query on a 131072-row list of 1M stays; one query on 262144 rows or more, or 16 on 131072, go.)
+ *   bm25_rows_scan_gain (80), bm25_rows_scan_floor (20)   the sparse rule: route iff  gain x sum over the lists of queries x rows  >
+ *                         N x (sub-queries + floor x cells) -- floor: what the scan route costs before its first sub-query and with every
+ *                         further class the batch is spread over, in sub-queries of scan work.
+ *                         Basis of the constants: profiles/rows_scan_timing.json (96 swept points, route off / every list / by the rule;
+ *                         DESIGN K11 names the points where the rule's choice or its cost is not the better arm's)
  *   dense_dir_block_min_rows (4096)  smallest dir that gets a block of its own
  *   bm25_long_tokens (28) packed shape: a batch whose longest query has MORE tokens than this scans with 32-bit sums (the bm25_small = 1
  *                         shape) -- 16-bit sums leave a query of nq tokens 65535 / nq payload levels and an error bound of 3 nq units, and
@@ -558,6 +603,8 @@ int erh_dense_exhaustive_count(erh_handle *h, int32_t *count);
  *   dense_tile384_nomem                                times the 384-row copy of the chunk matrix did not fit and the 256 x 256 scan took over
  *   dense_exhaustive_queries                           queries answered by the exhaustive path (device counter; summed over calls)
  *   dense_block_groups                                 query groups answered from their dir's block (dense_dir_blocks)
+ *   dense_block_builds                                 times the dir blocks were (re)built: the first filtered call after erh_set_dense /
+ *                                                      erh_set_doc_meta, and never because of a rows call on the scan route
  *   dense_grouped_launches                             calls whose block groups ran as one launch per stage (dense_group_launch)
  *   dense_group_reruns                                 block groups of routed calls that erh_dense_check / a host-output return ran again as pipelines of
  *                                                      their own because one of their queries was flagged (normally 0)
@@ -575,6 +622,8 @@ int erh_dense_exhaustive_count(erh_handle *h, int32_t *count);
  *                                                      of the long shape (one score + select pair per chunk of queries)
  *   bm25_sets_calls                                    erh_bm25_topk_sets calls (each also counts once in bm25_calls)
  *   bm25_sets_subqueries / bm25_sets_merge_launches    its (query, allowed class) sub-queries, summed over calls / its merge launches (one per call)
+ *   dense_rows_scan_calls / bm25_rows_scan_calls       rows calls (either entry) whose long lists took the scan route (each also counts once in *_rows_calls)
+ *   dense_rows_scan_subqueries / bm25_rows_scan_subqueries  their (query, cell) sub-queries, summed over calls
  *   bm25_mixed_launches                                BM25 scans launched with both bodies (bm25_mixed: a batch with queries longer than bm25_long_tokens)
  *   bm25_redo_segments                                 (query, segment) pairs the fixed-point scan handed to the exact block scan (device counter)
  * Reading a device counter synchronises the device.  Unknown name: ERH_ERR_INVALID. */
@@ -587,6 +636,14 @@ int erh_reset_stats(erh_handle *h);
  * top-k members inside it is ~Binomial(k, n0 / n), and `rank` or more of them land there with probability < 1e-7
  * (tests/test_speculation_rank.py); every query's threshold is verified on the device anyway. */
 int erh_dense_seed_rank(int k, int64_t n0, int64_t n);
+
+/* Debug, pure function (no handle, no device): the host step of the rows entries' scan route.  cell_sig uint64[n_cells]: the membership
+ * signatures of the call's cells (bit l: the cell's rows are in routed list l of n_routed); bit_of int32[B]: the bit of query b's list, -1 =
+ * the query is not on the route.  Writes sub_ptr int32[B + 1] and sub_cls int16[sub_ptr[B]] (capacity sub_cap): query b's class set = the
+ * cells whose signature has its bit, ascending.  ERH_ERR_UNSUPPORTED: the call falls back to the row-by-row shapes (n_routed > 64 or
+ * n_cells > 32766); ERH_ERR_NOMEM: sub_cap too small. */
+int erh_debug_rows_class_sets(int n_cells, const uint64_t *cell_sig, int n_routed, int B, const int32_t *bit_of, int32_t *sub_ptr,
+                              int16_t *sub_cls, int sub_cap);
 
 /* Debug: plain (non-MFMA) fp32 scores of B fp16 queries against rows [row0, row0+rows) of the stored
  * matrix, out float32[B*rows] on the host; and the MFMA scores of the same block. */

@@ -49,6 +49,9 @@ def section(args):
     dev = torch.device("cuda", 0)
     n, vocab, k = args.docs, args.vocab, args.k
     eng = RetrievalEngine(0)
+    # the `rows` arms here are the row-by-row shapes: the scan route of long lists (DESIGN K11) is off unless asked for -- its own sweep,
+    # both arms interleaved, is scripts/rows_scan_timing.py
+    eng.set_option("bm25_rows_scan", args.rows_scan)
     indptr, doc, tf, lens, flat = synth.token_csr_torch(n, vocab, seed=3, device=dev)
     eng.set_bm25(build_bm25_index_from_postings(indptr, doc, tf, lens, BM25S, compute_payload=False), payload_on_device=True)
     toks = synth.token_queries(flat, lens, vocab, 1024, seed=2000, lengths=synth.REF_QUESTION_LENGTHS)
@@ -174,6 +177,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--min-seconds", type=float, default=0.3)
     ap.add_argument("--max-row-scores", type=int, default=1 << 26)
+    ap.add_argument("--rows-scan", type=int, default=0, choices=(0, 1, 2),
+                    help="option bm25_rows_scan for every rows arm: 0 = the row-by-row shapes (default), 1 = by the work rule, 2 = every long list")
     ap.add_argument("--walk-queries", type=int, default=16)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bm25_rows_timing.json"))
     ap.add_argument("--section", default=None, help=argparse.SUPPRESS)
@@ -182,6 +187,8 @@ def main():
     if args.section:
         return section(args)
     rec = {"shape": {"docs": args.docs, "vocab": args.vocab, "variant": "bm25s", "k": args.k, "query_lengths": "the reference's 103 questions"},
+           "options": {"bm25_rows_scan": args.rows_scan, "note": "the `rows` arms ran with this value; a default handle has 1 (lists of at least "
+                       "bm25_rows_scan_min_rows rows go through the scan where the work rule says so: scripts/rows_scan_timing.py)"},
            "choices": ROWS_CHOICES,
            "method": {"reps": args.reps, "min_seconds": args.min_seconds, "column": "erh_bm25_topk + erh_sync, default options",
                       "rows": "erh_bm25_topk_rows + erh_sync, tables uploaded by every call"}, "sections": {}}
@@ -190,7 +197,7 @@ def main():
             part = os.path.join(tmp, sec + ".json")
             cmd = [sys.executable, os.path.abspath(__file__), "--section", sec, "--part", part, "--docs", str(args.docs), "--vocab", str(args.vocab),
                    "--dim", str(args.dim), "--k", str(args.k), "--steps", str(args.steps), "--reps", str(args.reps),
-                   "--min-seconds", str(args.min_seconds), "--max-row-scores", str(args.max_row_scores), "--walk-queries", str(args.walk_queries)]
+                   "--min-seconds", str(args.min_seconds), "--max-row-scores", str(args.max_row_scores), "--rows-scan", str(args.rows_scan), "--walk-queries", str(args.walk_queries)]
             try:
                 rc = subprocess.run(cmd, timeout=LIMIT_S[sec]).returncode
             except subprocess.TimeoutExpired:

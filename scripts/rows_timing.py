@@ -63,6 +63,9 @@ def section(args):
     dev = torch.device("cuda", 0)
     n, d, k = args.chunks, args.dim, args.k
     eng = RetrievalEngine(0)
+    # the `rows` arms here are the row-by-row shapes: the scan route of long lists (DESIGN K11) is off unless asked for -- its own sweep,
+    # both arms interleaved, is scripts/rows_scan_timing.py
+    eng.set_option("dense_rows_scan", args.rows_scan)
     x = synth.dense_corpus_torch(n, d, seed=2, device=dev)
     eng.set_dense(x)
     qall = synth.dense_queries_torch(x, 1024, seed=1000)
@@ -157,13 +160,18 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--min-seconds", type=float, default=0.3)
     ap.add_argument("--max-row-scores", type=int, default=1 << 26)
+    ap.add_argument("--rows-scan", type=int, default=0, choices=(0, 1, 2),
+                    help="option dense_rows_scan for every rows arm: 0 = the row-by-row shapes (default), 1 = by the work rule, 2 = every long list")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dense_rows_timing.json"))
     ap.add_argument("--section", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--part", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.section:
         return section(args)
-    rec = {"shape": {"chunks": args.chunks, "dim": args.dim, "k": args.k}, "choices": ROWS_CHOICES,
+    rec = {"shape": {"chunks": args.chunks, "dim": args.dim, "k": args.k},
+           "options": {"dense_rows_scan": args.rows_scan, "note": "the `rows` arms ran with this value; a default handle has 1 (lists of at least "
+                       "dense_rows_scan_min_rows rows go through the scan where the work rule says so: scripts/rows_scan_timing.py)"},
+           "choices": ROWS_CHOICES,
            "method": {"reps": args.reps, "min_seconds": args.min_seconds, "column": "erh_dense_topk + erh_dense_check, default options",
                       "rows": "erh_dense_topk_rows + erh_sync, tables uploaded by every call"}, "sections": {}}
     with tempfile.TemporaryDirectory() as tmp:
@@ -171,7 +179,7 @@ def main():
             part = os.path.join(tmp, sec + ".json")
             cmd = [sys.executable, os.path.abspath(__file__), "--section", sec, "--part", part, "--chunks", str(args.chunks), "--dim", str(args.dim),
                    "--k", str(args.k), "--steps", str(args.steps), "--reps", str(args.reps), "--min-seconds", str(args.min_seconds),
-                   "--max-row-scores", str(args.max_row_scores)]
+                   "--max-row-scores", str(args.max_row_scores), "--rows-scan", str(args.rows_scan)]
             try:
                 rc = subprocess.run(cmd, timeout=LIMIT_S[sec]).returncode
             except subprocess.TimeoutExpired:

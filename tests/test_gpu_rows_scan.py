@@ -1,0 +1,776 @@
+"""GPU parity of the rows entries' scan route (DESIGN K11): the long lists of an erh_dense_topk_rows / erh_bm25_topk_rows call numbered as a
+call-local class column (csrc/rows_classes.hip) and answered by the sets pipelines on that column.  The reference of every parity check is
+the oracle's masked ranking, as in test_gpu_dense_rows.py / test_gpu_bm25_rows.py (the helpers are copied from there), and the same call with
+the route off (`*_rows_scan` = 0) must give the same bytes.  Every test asserts the route through the new counters.
+
+The tests run on a handle of their own with `*_rows_scan_min_rows` = 2049 and `*_rows_scan` = 2 (every eligible list), so that corpora of
+20 000 - 40 000 rows reach the route; the two full-size cases at the end run with the default options."""
+import numpy as np
+import pytest
+
+from easyrag_amd import _lib, synth
+from easyrag_amd.engine import RetrievalEngine, queries_to_csr
+from easyrag_amd.index import BM25S, OKAPI, build_bm25_index
+from oracle import BM25Okapi, BM25SLucene, bm25_filter, dense_exact_topk, to_f16_unit
+from oracle.dense import dense_exact_scores
+
+pytestmark = pytest.mark.gpu
+
+NB = 5                                     # distinct dense query vectors per corpus: query b carries vector b % NB
+NQ = 8                                     # distinct BM25 queries per corpus
+DENSE_KS = (1, 100, 768)
+BM25_KS = (10, 192, 1024)
+DSTATS = ("dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches", "dense_rows_scan_calls", "dense_rows_scan_subqueries")
+BSTATS = ("bm25_rows_calls", "bm25_rows_short_launches", "bm25_rows_long_launches", "bm25_rows_scan_calls", "bm25_rows_scan_subqueries")
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = RetrievalEngine(0)
+    for route in ("dense", "bm25"):
+        e.set_option(route + "_rows_scan_min_rows", 2049)
+        e.set_option(route + "_rows_scan", 2)
+    yield e
+    e.close()
+
+
+def _bits(a):
+    return np.asarray(a, np.float64).view(np.uint64)
+
+
+def _same_bytes(a, b):
+    for x, y in zip(a, b):
+        x = x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+        y = y.cpu().numpy() if hasattr(y, "cpu") else np.asarray(y)
+        assert np.array_equal(x.view(np.uint8), y.view(np.uint8))
+
+
+def _pick(rng, pool, length):
+    pool = np.arange(pool, dtype=np.int64) if np.isscalar(pool) else np.asarray(pool, np.int64)
+    if length >= pool.shape[0]:
+        return pool.copy()
+    return np.sort(rng.choice(pool, size=length, replace=False))
+
+
+def _moved(engine, names, before):
+    after = {n: engine.stat(n) for n in names}
+    return {n: after[n] - before[n] for n in names}, after
+
+
+def _stats(engine, names):
+    return {n: engine.stat(n) for n in names}
+
+
+def _off(engine, route, fn):
+    """fn() with the route off: the parity arm."""
+    engine.set_option(route + "_rows_scan", 0)
+    try:
+        return fn()
+    finally:
+        engine.set_option(route + "_rows_scan", 2)
+
+
+def _list_cases(n, rng):
+    """name -> (lists, list_of): the list layouts of the issue.  Every list has at least 2049 rows."""
+    blocks = np.array_split(np.arange(n, dtype=np.int64), 70)               # ~n / 70 rows each; six of them: > 2049 for n >= 24000
+    sixty_four = [np.concatenate(blocks[l:l + 6]) for l in range(64)]
+    assert min(len(r) for r in sixty_four) >= 2049
+    a, b = _pick(rng, n, n // 3), _pick(rng, n, n // 2)
+    nest0 = _pick(rng, n, n // 2)
+    nest1 = _pick(rng, nest0, n // 4)
+    nest2 = _pick(rng, nest1, 2049)
+    lo40 = (np.arange(40) % 2).astype(np.int32)
+    return {
+        "one shared list, 1 query": ([_pick(rng, n, 2049)], np.zeros(1, np.int32)),
+        "one shared list, 40 queries": ([_pick(rng, n, 9001)], np.zeros(40, np.int32)),
+        "two overlapping lists": ([a, b], lo40),
+        "nested lists": ([nest0, nest1, nest2], (np.arange(17) % 3).astype(np.int32)),
+        "disjoint lists": ([np.arange(0, 5000, dtype=np.int64), np.arange(7000, n, 2, dtype=np.int64)], lo40[:9]),
+        "all rows": ([np.arange(n, dtype=np.int64), a], lo40[:6]),
+        "64 lists": (sixty_four, (np.arange(64, dtype=np.int32) * 37) % 64),
+    }
+
+
+# ---- dense ------------------------------------------------------------------------------------------------------------------------------
+def _unit16(n, d, rng):
+    out = np.empty((n, d), np.float16)
+    for r0 in range(0, n, 8192):
+        out[r0:r0 + 8192] = to_f16_unit(rng.standard_normal((min(8192, n - r0), d), dtype=np.float32))
+    return out
+
+
+_DENSE = {}
+
+
+def _dense_corpus(d):
+    """(x16 [N x d], base query vectors [NB x d], oracle score vectors [NB x N]); N is odd and no multiple of any tile."""
+    if d not in _DENSE:
+        rng = np.random.default_rng(2000 + d)
+        n = 30011 if d <= 128 else 24007
+        x = _unit16(n, d, rng)
+        base = to_f16_unit(x[rng.integers(0, n, NB)].astype(np.float32) + 0.7 * rng.standard_normal((NB, d)).astype(np.float32) / np.sqrt(d))
+        S = np.stack([dense_exact_scores(x, base[j]) for j in range(NB)])
+        _DENSE[d] = (x, base, S)
+    return _DENSE[d]
+
+
+def _dense_rank(scores, rows, k):
+    rows = np.asarray(rows, np.int64)
+    s = scores[rows]
+    order = np.lexsort((rows, -s))[:k]
+    return rows[order], s[order]
+
+
+def _dense_check(got, S, lists, list_of, k, who=""):
+    ids, sc, ln = (np.asarray(a.cpu()) if hasattr(a, "cpu") else np.asarray(a) for a in got)
+    for b in range(len(list_of)):
+        l = int(list_of[b])
+        rows = np.zeros(0, np.int64) if l < 0 else lists[l]
+        oid, osc = _dense_rank(S[b % NB], rows, k)
+        assert ln[b] == min(k, len(rows)) == len(oid), (who, b)
+        assert np.array_equal(ids[b, :ln[b]], oid), (who, b)
+        assert np.array_equal(_bits(sc[b, :ln[b]]), _bits(osc)), (who, b)
+        assert np.all(ids[b, ln[b]:] == -1) and np.all(sc[b, ln[b]:] == 0.0), (who, b)
+
+
+@pytest.mark.parametrize("d", [128, 1024])
+def test_dense_parity_sweep(eng, d):
+    x, base, S = _dense_corpus(d)
+    n = x.shape[0]
+    eng.set_dense(x)
+    eng.set_doc_meta(n, None, None)
+    cases = _list_cases(n, np.random.default_rng(d))
+    st = _stats(eng, DSTATS)
+    for name, (lists, lo) in cases.items():
+        q = base[np.arange(len(lo)) % NB]
+        for k in DENSE_KS if d == 128 else (100,):
+            got = eng.dense_topk_rows(q, k, lists, list_of=lo)
+            mv, st = _moved(eng, DSTATS, st)
+            assert (mv["dense_rows_calls"], mv["dense_rows_scan_calls"], mv["dense_rows_long_launches"]) == (1, 1, 0), (name, k, mv)
+            assert mv["dense_rows_scan_subqueries"] >= len(lo), (name, k, mv)
+            _dense_check(got, S, lists, lo, k, (name, k))
+            want = _off(eng, "dense", lambda: eng.dense_topk_rows(q, k, lists, list_of=lo))
+            mv, st = _moved(eng, DSTATS, st)
+            assert mv["dense_rows_scan_calls"] == 0 and mv["dense_rows_long_launches"] >= 1, (name, k, mv)
+            _same_bytes(got, want)
+    # the cells of two overlapping lists are three, of one list one: the sub-query counts say so
+    lists, lo = cases["two overlapping lists"]
+    eng.dense_topk_rows(base[np.arange(40) % NB], 10, lists, list_of=lo)
+    mv, st = _moved(eng, DSTATS, st)
+    assert mv["dense_rows_scan_subqueries"] == 80, mv                        # every query: its list's own cell + the shared one
+    assert eng.dense_diag()["uncertified"] == 0
+
+
+def test_dense_ties_across_cells(eng):
+    """Exact duplicates of the query placed in different cells of one list: the merge orders them by ascending row id, and two runs of the
+    call give the same bytes although the cells are numbered in arrival order."""
+    rng = np.random.default_rng(41)
+    n, d = 24001, 128
+    x = _unit16(n, d, rng)
+    hot = x[5].copy()
+    a, b = np.arange(0, 12000, dtype=np.int64), np.arange(6000, 20000, dtype=np.int64)      # cells: a only, a and b, b only
+    dup = np.sort(np.concatenate([[5], rng.choice(np.arange(6, 6000), 14, replace=False), rng.choice(np.arange(6000, 12000), 15, replace=False),
+                                  rng.choice(np.arange(12000, 20000), 10, replace=False)]))
+    x[dup] = hot
+    eng.set_dense(x)
+    eng.set_doc_meta(n, None, None)
+    q = np.stack([hot, hot, hot])
+    lo = np.array([0, 1, 0], np.int32)
+    s = dense_exact_scores(x, hot)
+    st = _stats(eng, DSTATS)
+    for k in (20, 35):                                                       # cuts inside the tied run of both lists
+        got = eng.dense_topk_rows(q, k, [a, b], list_of=lo)
+        mv, st = _moved(eng, DSTATS, st)
+        assert (mv["dense_rows_scan_calls"], mv["dense_rows_long_launches"], mv["dense_rows_scan_subqueries"]) == (1, 0, 6), mv
+        for j, rows in enumerate((a, b, a)):
+            oid, osc = _dense_rank(s, rows, k)
+            assert np.array_equal(got[0][j], oid) and np.array_equal(_bits(got[1][j]), _bits(osc)), (k, j)
+        tied = got[0][0][got[1][0] == got[1][0, 0]]
+        in_a = dup[dup < 12000]
+        assert len(tied) == min(k, len(in_a)) and np.array_equal(tied, in_a[:len(tied)])      # ascending ids across the two cells of `a`
+        assert tied[-1] >= 6000 or k < 16                                    # (the run really crosses the cell boundary)
+        _same_bytes(got, eng.dense_topk_rows(q, k, [a, b], list_of=lo))
+        mv, st = _moved(eng, DSTATS, st)
+
+
+def test_dense_mixed_call(eng):
+    """No list, a short list, a long list below the minimum, and routed lists in one batch: each group on its own shape."""
+    x, base, S = _dense_corpus(128)
+    n = x.shape[0]
+    eng.set_dense(x)
+    eng.set_doc_meta(n, None, None)
+    rng = np.random.default_rng(7)
+    lists = [_pick(rng, n, 300), _pick(rng, n, 3000), _pick(rng, n, 8000), _pick(rng, n, 5000), _pick(rng, n, 2048)]
+    lo = np.array([-1, 0, 1, 2, 3, 2, 4, 1, -1, 3, 0, 2], np.int32)
+    q = base[np.arange(len(lo)) % NB]
+    eng.set_option("dense_rows_scan_min_rows", 5000)
+    try:
+        st = _stats(eng, DSTATS)
+        got = eng.dense_topk_rows(q, 100, lists, list_of=lo)
+        mv, st = _moved(eng, DSTATS, st)
+        assert mv == {"dense_rows_calls": 1, "dense_rows_short_launches": 1, "dense_rows_long_launches": 1, "dense_rows_scan_calls": 1,
+                      "dense_rows_scan_subqueries": mv["dense_rows_scan_subqueries"]}, mv
+        assert mv["dense_rows_scan_subqueries"] >= 5                         # five queries on the two routed lists
+        _dense_check(got, S, lists, lo, 100, "mixed")
+        want = _off(eng, "dense", lambda: eng.dense_topk_rows(q, 100, lists, list_of=lo))
+        _same_bytes(got, want)
+    finally:
+        eng.set_option("dense_rows_scan_min_rows", 2049)
+
+
+def test_dense_fallbacks(eng):
+    import torch
+    x, base, S = _dense_corpus(128)
+    n = x.shape[0]
+    eng.set_dense(x)
+    eng.set_doc_meta(n, None, None)
+    rng = np.random.default_rng(13)
+    blocks = np.array_split(np.arange(n, dtype=np.int64), 72)
+    lists = [np.concatenate(blocks[l:l + 6]) for l in range(65)]             # 65 routable lists: one more than a signature has bits
+    lo = np.arange(65, dtype=np.int32)
+    q = base[np.arange(65) % NB]
+    st = _stats(eng, DSTATS)
+    got = eng.dense_topk_rows(q, 100, lists, list_of=lo)
+    mv, st = _moved(eng, DSTATS, st)
+    assert mv["dense_rows_calls"] == 1 and mv["dense_rows_scan_calls"] == 0 and mv["dense_rows_long_launches"] >= 1, mv
+    _dense_check(got, S, lists, lo, 100, "65 lists")
+    got = eng.dense_topk_rows(q[:64], 100, lists[:64], list_of=lo[:64])      # 64 of them go
+    mv, st = _moved(eng, DSTATS, st)
+    assert mv["dense_rows_scan_calls"] == 1 and mv["dense_rows_long_launches"] == 0, mv
+    # the option at 0
+    one = [_pick(rng, n, 6000)]
+    got = _off(eng, "dense", lambda: eng.dense_topk_rows(q[:9], 100, one, list_of=np.zeros(9, np.int32)))
+    mv, st = _moved(eng, DSTATS, st)
+    assert (mv["dense_rows_calls"], mv["dense_rows_scan_calls"], mv["dense_rows_long_launches"]) == (1, 0, 1), mv
+    _dense_check(got, S, one, np.zeros(9, np.int32), 100, "option 0")
+    # a rows call between a device-output erh_dense_topk and its check keeps today's shape and leaves that call's work space alone
+    qd = torch.from_numpy(base).cuda()
+    dev = eng.dense_topk(qd, 100, device_out=True)
+    rows_dev = eng.dense_topk_rows(qd, 100, one, list_of=np.zeros(NB, np.int32), device_out=True)
+    mv, st = _moved(eng, DSTATS, st)
+    assert (mv["dense_rows_calls"], mv["dense_rows_scan_calls"], mv["dense_rows_long_launches"]) == (1, 0, 1), mv
+    eng.dense_check()
+    ids, sc, ln = (a.cpu().numpy() for a in dev)
+    for b in range(NB):
+        oid, osc = _dense_rank(S[b], np.arange(n), 100)
+        assert ln[b] == 100 and np.array_equal(ids[b], oid) and np.array_equal(_bits(sc[b]), _bits(osc)), b
+    _dense_check(rows_dev, S, one, np.zeros(NB, np.int32), 100, "between a call and its check")
+    # ... and behind the check the same call takes the route again
+    again = eng.dense_topk_rows(qd, 100, one, list_of=np.zeros(NB, np.int32), device_out=True)
+    eng.sync()
+    mv, st = _moved(eng, DSTATS, st)
+    assert mv["dense_rows_scan_calls"] == 1 and mv["dense_rows_long_launches"] == 0, mv
+    _same_bytes(rows_dev, again)
+
+
+def test_dense_outputs_streams_and_query_types(eng):
+    import torch
+    x, base, S = _dense_corpus(128)
+    n, d = x.shape
+    eng.set_dense(x)
+    eng.set_doc_meta(n, None, None)
+    rng = np.random.default_rng(17)
+    lists = [_pick(rng, n, 7000), _pick(rng, n, 2049)]
+    lo = (np.arange(11) % 2).astype(np.int32)
+    q = base[np.arange(11) % NB]
+    k = 100
+    host = eng.dense_topk_rows(q, k, lists, list_of=lo)
+    _dense_check(host, S, lists, lo, k, "host")
+    dev = torch.device("cuda", 0)
+    s2 = torch.cuda.Stream(device=dev)
+    qd = torch.from_numpy(q).to(dev)
+    torch.cuda.synchronize()
+    st = _stats(eng, DSTATS)
+    out = eng.dense_topk_rows(qd, k, lists, list_of=lo, device_out=True, stream=s2)
+    eng.sync(s2)                                                             # final after the sync: no dense_check
+    mv, st = _moved(eng, DSTATS, st)
+    assert mv["dense_rows_scan_calls"] == 1 and mv["dense_rows_long_launches"] == 0, mv
+    _same_bytes(host, out)
+    eng.dense_check(s2)                                                      # nothing is left for it
+    _same_bytes(host, out)
+    assert eng.dense_diag()["exhaustive"] == 0
+    _same_bytes(host, eng.dense_topk_rows(q.astype(np.float32), k, lists, list_of=lo))     # fp16 values widened: the rounding is the identity
+    # normalize_q on the device: +-0.5 entries normalise exactly to +-1 / sqrt(d)
+    sign = np.where(rng.random((11, d)) < 0.5, -1.0, 1.0)
+    want_q = (sign / np.sqrt(d)).astype(np.float16)
+    for q_in in ((0.5 * sign).astype(np.float32), (0.5 * sign).astype(np.float16)):
+        ids, sc, ln = eng.dense_topk_rows(q_in, k, lists, list_of=lo, normalize_q=True)
+        for b in range(11):
+            mask = np.zeros(n, bool)
+            mask[lists[lo[b]]] = True
+            oid, osc = dense_exact_topk(x, want_q[b], k, mask)
+            assert ln[b] == len(oid) and np.array_equal(ids[b, :ln[b]], oid) and np.array_equal(_bits(sc[b, :ln[b]]), _bits(osc)), b
+    mv, st = _moved(eng, DSTATS, st)
+    assert mv["dense_rows_scan_calls"] == 3 and mv["dense_rows_long_launches"] == 0, mv
+
+
+def test_dense_error_path_and_state(eng):
+    """A malformed list is refused before anything is enqueued; the handle's own class column serves filtered calls before and after routed
+    calls (the dir block included); without a class column a filtered call still fails."""
+    x, base, S = _dense_corpus(128)
+    n = x.shape[0]
+    rng = np.random.default_rng(19)
+    sizes = [9000, 300, 7000, n - 16300]
+    dir_id = np.repeat(np.arange(4), sizes).astype(np.int16)
+    tail = dir_id[sizes[0]:].copy()                                          # class 0 stays one contiguous run (a block), the rest is shuffled
+    rng.shuffle(tail)
+    dir_id[sizes[0]:] = tail
+    eng.set_dense(x)
+    eng.set_doc_meta(n, None, dir_id)
+    col = (np.arange(NB) % 4).astype(np.int16)
+    col0 = np.zeros(NB, np.int16)
+    groups = eng.stat("dense_block_groups")
+    first = eng.dense_topk(base, 100, filter_dir=col0)                       # builds the block of class 0 and scans it
+    assert eng.stat("dense_block_groups") > groups
+    mixed = eng.dense_topk(base, 100, filter_dir=col)
+    for got_, c_ in ((first, col0), (mixed, col)):
+        for b in range(NB):
+            oid, osc = _dense_rank(S[b], np.flatnonzero(dir_id == c_[b]), 100)
+            assert np.array_equal(got_[0][b], oid) and np.array_equal(_bits(got_[1][b]), _bits(osc)), b
+    lists = [_pick(rng, n, 9000), _pick(rng, n, 4000)]
+    lo = (np.arange(NB) % 2).astype(np.int32)
+    # the error path: rows not ascending -- ERH_ERR_INVALID, outputs untouched, no counter moved
+    st = _stats(eng, DSTATS)
+    bad = np.concatenate([lists[0][:5000][::-1], lists[1]]).astype(np.int32)
+    ptr = np.array([0, 5000, 5000 + len(lists[1])], np.int64)
+    q = np.ascontiguousarray(base)
+    ids = np.full((NB, 3), 77, np.int32)
+    sc = np.full((NB, 3), 7.5, np.float64)
+    ln = np.full(NB, 77, np.int32)
+    rc = eng._lib.erh_dense_topk_rows(eng._h, q.ctypes.data, _lib.ERH_F16, 0, 0, NB, 3, 2, ptr.ctypes.data, bad.ctypes.data, lo.ctypes.data,
+                                      ids.ctypes.data, sc.ctypes.data, ln.ctypes.data, 0, 0)
+    assert rc == _lib.ERH_ERR_INVALID and np.all(ids == 77) and np.all(sc == 7.5) and np.all(ln == 77)
+    assert _moved(eng, DSTATS, st)[0] == dict.fromkeys(DSTATS, 0)
+    _same_bytes(mixed, eng.dense_topk(base, 100, filter_dir=col))
+    # a routed call, then the filtered call again: same answer, the dir block still serves class 0
+    got = eng.dense_topk_rows(base, 100, lists, list_of=lo)
+    mv, st = _moved(eng, DSTATS, st)
+    assert mv["dense_rows_scan_calls"] == 1 and mv["dense_rows_long_launches"] == 0, mv
+    _dense_check(got, S, lists, lo, 100, "routed, class column set")
+    groups, builds = eng.stat("dense_block_groups"), eng.stat("dense_block_builds")
+    assert builds >= 1                                                       # (the first filtered call built them)
+    _same_bytes(first, eng.dense_topk(base, 100, filter_dir=col0))
+    assert eng.stat("dense_block_groups") > groups
+    assert eng.stat("dense_block_builds") == builds                          # ... and the swap handed them back: no rebuild
+    _same_bytes(mixed, eng.dense_topk(base, 100, filter_dir=col))
+    assert eng.get_option("dense_dir_blocks") == 1
+    _same_bytes(eng.dense_topk_sets(base, 100, [[0, 2]] * NB), eng.dense_topk_sets(base, 100, [[2, 0]] * NB))
+    # no class column: a routed call does not leave one behind
+    eng.set_doc_meta(n, None, None)
+    eng.dense_topk_rows(base, 100, lists, list_of=lo)
+    mv, st = _moved(eng, DSTATS, st)
+    assert mv["dense_rows_scan_calls"] == 1, mv
+    with pytest.raises(_lib.ErhError) as ei:
+        eng.dense_topk(base, 100, filter_dir=col)
+    assert ei.value.status == _lib.ERH_ERR_STATE
+
+
+def _random_halves(n, n_lists, rng):
+    """n_lists independent random halves of n rows: nearly every row has a membership word of its own."""
+    member = rng.random((n_lists, n)) < 0.5
+    words = np.zeros(n, np.uint64)
+    for l in range(n_lists):
+        words |= member[l].astype(np.uint64) << np.uint64(l)
+    return [np.flatnonzero(member[l]).astype(np.int64) for l in range(n_lists)], int(np.unique(words[words != 0]).shape[0])
+
+
+def test_dense_more_cells_than_the_column_numbers(eng):
+    """24 overlapping random lists over 40 009 rows: about 40 000 cells, more than the 32 766 an int16 column numbers.  The classification
+    gives up (it stops claiming slots with the claim that exceeds the bound; no probe runs the length of the table) and the whole call is
+    answered on the row-by-row shapes, without error and with the right answer."""
+    rng = np.random.default_rng(29)
+    n, d, n_lists = 40009, 128, 24
+    x = _unit16(n, d, rng)
+    base = to_f16_unit(x[rng.integers(0, n, NB)].astype(np.float32) + 0.7 * rng.standard_normal((NB, d)).astype(np.float32) / np.sqrt(d))
+    S = np.stack([dense_exact_scores(x, base[j]) for j in range(NB)])
+    lists, cells = _random_halves(n, n_lists, rng)
+    assert cells > 32766 and min(len(r) for r in lists) >= 2049
+    lo = np.arange(n_lists, dtype=np.int32)
+    q = base[np.arange(n_lists) % NB]
+    eng.set_dense(x)
+    eng.set_doc_meta(n, None, None)
+    st = _stats(eng, DSTATS)
+    got = eng.dense_topk_rows(q, 100, lists, list_of=lo)
+    mv, st = _moved(eng, DSTATS, st)
+    assert (mv["dense_rows_calls"], mv["dense_rows_scan_calls"], mv["dense_rows_scan_subqueries"]) == (1, 0, 0), mv
+    assert mv["dense_rows_long_launches"] >= 1, mv
+    _dense_check(got, S, lists, lo, 100, "too many cells")
+    # half of the lists: 2^12 - 1 cells at the most, and the same handle routes again
+    got = eng.dense_topk_rows(q[:12], 100, lists[:12], list_of=lo[:12])
+    mv, st = _moved(eng, DSTATS, st)
+    assert mv["dense_rows_scan_calls"] == 1 and mv["dense_rows_long_launches"] == 0, mv
+    _dense_check(got, S, lists[:12], lo[:12], 100, "4095 cells")
+
+
+# ---- BM25 -------------------------------------------------------------------------------------------------------------------------------
+BN, VOCAB = 30011, 2000
+
+
+def _oracle_for(variant, docs):
+    return BM25Okapi(docs, k1=1.5, b=0.75, epsilon=0.25) if variant == OKAPI else BM25SLucene(k1=1.5, b=0.75).index(docs)
+
+
+def _scores(ora, q, n):
+    if len(q) == 0:
+        return np.zeros(n, np.float64)
+    return np.asarray(ora.get_scores(list(q))).astype(np.float64)
+
+
+def _bm25_rank(scores, rows, k):
+    rows = np.asarray(rows, np.int64)
+    s = scores[rows]
+    rows, s = rows[s > 0], s[s > 0]
+    order = np.lexsort((rows, -s))[:k]
+    return rows[order], s[order]
+
+
+def _bm25_check(got, S_of, lists, list_of, k, who=""):
+    ids, sc, ln = (np.asarray(a.cpu()) if hasattr(a, "cpu") else np.asarray(a) for a in got)
+    B = len(list_of)
+    assert ids.shape == (B, k) and sc.shape == (B, k) and ln.shape == (B,)
+    for b in range(B):
+        l = int(list_of[b])
+        rows = np.zeros(0, np.int64) if l < 0 else lists[l]
+        oid, osc = _bm25_rank(S_of(b), rows, k)
+        assert ln[b] == len(oid), (who, b, int(ln[b]), len(oid))
+        assert np.array_equal(ids[b, :ln[b]], oid), (who, b)
+        assert np.array_equal(_bits(sc[b, :ln[b]]), _bits(osc)), (who, b)
+        assert np.all(ids[b, ln[b]:] == -1) and np.all(sc[b, ln[b]:] == 0.0), (who, b)
+
+
+_BM25 = {}
+
+
+def _bm25_corpus(variant):
+    if variant not in _BM25:
+        flat, lens = synth.token_corpus(BN, VOCAB, seed=2, mean_len=20)
+        docs = [list(map(int, d)) for d in synth.split_docs(flat, lens)]
+        ora = _oracle_for(variant, docs)
+        idx = build_bm25_index(docs, variant)
+        queries = [list(map(int, q)) for q in synth.token_queries(flat, lens, VOCAB, NQ, seed=9)]
+        S = np.stack([_scores(ora, q, BN) for q in queries])
+        _BM25[variant] = dict(ora=ora, idx=idx, queries=queries, S=S)
+    return _BM25[variant]
+
+
+def _csr(idx, queries):
+    return queries_to_csr([idx.tokens_to_ids(q) for q in queries])
+
+
+@pytest.mark.parametrize("variant", [OKAPI, BM25S])
+def test_bm25_parity_sweep(eng, variant):
+    c = _bm25_corpus(variant)
+    idx, S = c["idx"], c["S"]
+    eng.set_bm25(idx)
+    eng.set_doc_meta(BN, None, None)
+    cases = _list_cases(BN, np.random.default_rng(11 + variant))
+    st = _stats(eng, BSTATS)
+    others = _stats(eng, ("bm25_calls", "bm25_sets_calls"))
+    for name, (lists, lo) in cases.items():
+        csr = _csr(idx, [c["queries"][b % NQ] for b in range(len(lo))])
+        for k in BM25_KS:
+            got = eng.bm25_topk_rows(*csr, k, lists, list_of=lo)
+            mv, st = _moved(eng, BSTATS, st)
+            assert (mv["bm25_rows_calls"], mv["bm25_rows_scan_calls"], mv["bm25_rows_long_launches"]) == (1, 1, 0), (name, k, mv)
+            assert mv["bm25_rows_scan_subqueries"] >= len(lo), (name, k, mv)
+            _bm25_check(got, lambda b: S[b % NQ], lists, lo, k, (name, k))
+            want = _off(eng, "bm25", lambda: eng.bm25_topk_rows(*csr, k, lists, list_of=lo))
+            mv, st = _moved(eng, BSTATS, st)
+            assert mv["bm25_rows_scan_calls"] == 0 and mv["bm25_rows_long_launches"] >= 1, (name, k, mv)
+            _same_bytes(got, want)
+    # the cells' row ranges or all tiles: the same bytes
+    lists, lo = cases["disjoint lists"]
+    csr = _csr(idx, [c["queries"][b % NQ] for b in range(len(lo))])
+    a = eng.bm25_topk_rows(*csr, 192, lists, list_of=lo)
+    eng.set_option("bm25_dir_range", 0)
+    try:
+        _same_bytes(a, eng.bm25_topk_rows(*csr, 192, lists, list_of=lo))
+    finally:
+        eng.set_option("bm25_dir_range", 1)
+    assert _moved(eng, ("bm25_calls", "bm25_sets_calls"), others)[0] == {"bm25_calls": 0, "bm25_sets_calls": 0}   # a routed call is not a sets call
+
+
+def test_bm25_okapi_index_with_non_positive_payloads(eng):
+    """rank-bm25's epsilon * average_idf floor is negative when most terms sit in most documents: the fixed-point scan does not apply and the
+    order-keeping scans answer the routed sub-queries."""
+    rng = np.random.default_rng(8)
+    docs = []
+    for _ in range(9000):
+        doc = [t for t in range(6) if rng.random() < 0.8] or [0]
+        doc += [int(t) for t in rng.integers(0, 6, size=rng.integers(0, 4))]
+        doc += [6] * (rng.random() < 0.1) + [7] * (rng.random() < 0.1)
+        docs.append(doc)
+    ora = _oracle_for(OKAPI, docs)
+    idx = build_bm25_index(docs, OKAPI)
+    assert float(idx.payload.min()) < 0.0 < float(idx.payload.max())
+    eng.set_bm25(idx)
+    eng.set_doc_meta(9000, None, None)
+    queries = [[0, 1, 7], [6, 7, 2, 2], [7], [3], [6, 0, 1, 2, 3, 4, 5]]
+    Sq = [_scores(ora, q, 9000) for q in queries]
+    lists = [np.arange(9000, dtype=np.int64), _pick(rng, 9000, 5000), _pick(rng, 9000, 2049)]
+    lo = np.array([0, 1, 2, 1, 0], np.int32)
+    st = _stats(eng, BSTATS)
+    for k in (10, 192):
+        got = eng.bm25_topk_rows(*_csr(idx, queries), k, lists, list_of=lo)
+        mv, st = _moved(eng, BSTATS, st)
+        assert mv["bm25_rows_scan_calls"] == 1 and mv["bm25_rows_long_launches"] == 0, mv
+        _bm25_check(got, lambda b: Sq[b], lists, lo, k, ("negative", k))
+    mask = np.zeros(9000, bool)
+    mask[lists[1]] = True
+    want = bm25_filter(ora.get_scores(queries[1]), 192, mask)               # the literal oracle once more
+    assert list(got[0][1, :got[2][1]]) == [w[0] for w in want] and list(got[1][1, :got[2][1]]) == [w[1] for w in want]
+
+
+@pytest.mark.parametrize("variant", [OKAPI, BM25S])
+def test_bm25_ties_across_cells(eng, variant):
+    """16 distinct documents repeated over the corpus: exact score ties in every cell of two overlapping lists, merged by ascending row id;
+    two runs give the same bytes."""
+    rng = np.random.default_rng(4)
+    base = [list(map(int, rng.integers(0, 12, size=rng.integers(3, 9)))) for _ in range(16)]
+    n = 8000
+    docs = [base[i % 16] for i in range(n)]
+    ora = _oracle_for(variant, docs)
+    idx = build_bm25_index(docs, variant)
+    eng.set_bm25(idx)
+    eng.set_doc_meta(n, None, None)
+    queries = [[0, 1, 2], [5], [3, 3, 7, 11], [2, 9]]
+    lists = [np.arange(0, 5000, dtype=np.int64), np.arange(2500, n, dtype=np.int64)]
+    lo = np.array([0, 1, 0, 1], np.int32)
+    Sq = [_scores(ora, q, n) for q in queries]
+    st = _stats(eng, BSTATS)
+    for k in (7, 1024):
+        got = eng.bm25_topk_rows(*_csr(idx, queries), k, lists, list_of=lo)
+        mv, st = _moved(eng, BSTATS, st)
+        assert (mv["bm25_rows_scan_calls"], mv["bm25_rows_long_launches"], mv["bm25_rows_scan_subqueries"]) == (1, 0, 8), mv
+        _bm25_check(got, lambda b: Sq[b], lists, lo, k, ("ties", k))
+        _same_bytes(got, eng.bm25_topk_rows(*_csr(idx, queries), k, lists, list_of=lo))
+        mv, st = _moved(eng, BSTATS, st)
+    ids, sc, ln = got
+    assert ln[0] > 20 and len(np.unique(sc[0, :ln[0]])) <= 16 and ids[0, :ln[0]].max() >= 2500   # tied runs that cross the cells of list 0
+
+
+def test_bm25_more_cells_than_the_column_numbers(eng):
+    """The sparse twin of test_dense_more_cells_than_the_column_numbers: about 40 000 cells, the call falls back whole and is right."""
+    rng = np.random.default_rng(31)
+    n, n_lists = 40009, 24
+    base = [list(map(int, rng.integers(0, 40, size=rng.integers(3, 12)))) for _ in range(997)]
+    docs = [base[i % 997] for i in range(n)]
+    ora = _oracle_for(BM25S, docs)
+    idx = build_bm25_index(docs, BM25S)
+    queries = [[0, 1, 2], [5, 17], [3, 3, 7, 11], [2, 39, 20]]
+    Sq = [_scores(ora, q, n) for q in queries]
+    lists, cells = _random_halves(n, n_lists, rng)
+    assert cells > 32766
+    lo = np.arange(n_lists, dtype=np.int32)
+    csr = _csr(idx, [queries[b % 4] for b in range(n_lists)])
+    eng.set_bm25(idx)
+    eng.set_doc_meta(n, None, None)
+    st = _stats(eng, BSTATS)
+    got = eng.bm25_topk_rows(*csr, 192, lists, list_of=lo)
+    mv, st = _moved(eng, BSTATS, st)
+    assert (mv["bm25_rows_calls"], mv["bm25_rows_scan_calls"], mv["bm25_rows_scan_subqueries"]) == (1, 0, 0), mv
+    assert mv["bm25_rows_long_launches"] >= 1, mv
+    _bm25_check(got, lambda b: Sq[b % 4], lists, lo, 192, "too many cells")
+    got = eng.bm25_topk_rows(*_csr(idx, [queries[b % 4] for b in range(12)]), 192, lists[:12], list_of=lo[:12])
+    mv, st = _moved(eng, BSTATS, st)
+    assert mv["bm25_rows_scan_calls"] == 1 and mv["bm25_rows_long_launches"] == 0, mv
+    _bm25_check(got, lambda b: Sq[b % 4], lists[:12], lo[:12], 192, "4095 cells")
+
+
+def test_bm25_mixed_call_fallbacks_and_errors(eng):
+    c = _bm25_corpus(OKAPI)
+    idx, S = c["idx"], c["S"]
+    eng.set_bm25(idx)
+    eng.set_doc_meta(BN, None, None)
+    rng = np.random.default_rng(23)
+    lists = [_pick(rng, BN, 300), _pick(rng, BN, 3000), _pick(rng, BN, 8000), _pick(rng, BN, 5000), _pick(rng, BN, 2048)]
+    lo = np.array([-1, 0, 1, 2, 3, 2, 4, 1, -1, 3, 0, 2], np.int32)
+    csr = _csr(idx, [c["queries"][b % NQ] for b in range(len(lo))])
+    eng.set_option("bm25_rows_scan_min_rows", 5000)
+    try:
+        st = _stats(eng, BSTATS)
+        got = eng.bm25_topk_rows(*csr, 192, lists, list_of=lo)
+        mv, st = _moved(eng, BSTATS, st)
+        assert (mv["bm25_rows_calls"], mv["bm25_rows_short_launches"], mv["bm25_rows_long_launches"], mv["bm25_rows_scan_calls"]) == (1, 1, 1, 1), mv
+        _bm25_check(got, lambda b: S[b % NQ], lists, lo, 192, "mixed")
+        _same_bytes(got, _off(eng, "bm25", lambda: eng.bm25_topk_rows(*csr, 192, lists, list_of=lo)))
+    finally:
+        eng.set_option("bm25_rows_scan_min_rows", 2049)
+    # 65 routable lists: today's shapes; 64: the route
+    blocks = np.array_split(np.arange(BN, dtype=np.int64), 72)
+    many = [np.concatenate(blocks[l:l + 6]) for l in range(65)]
+    lo65 = np.arange(65, dtype=np.int32)
+    csr65 = _csr(idx, [c["queries"][b % NQ] for b in range(65)])
+    st = _stats(eng, BSTATS)
+    got = eng.bm25_topk_rows(*csr65, 10, many, list_of=lo65)
+    mv, st = _moved(eng, BSTATS, st)
+    assert mv["bm25_rows_calls"] == 1 and mv["bm25_rows_scan_calls"] == 0 and mv["bm25_rows_long_launches"] >= 1, mv
+    _bm25_check(got, lambda b: S[b % NQ], many, lo65, 10, "65 lists")
+    # the option at 0
+    got = _off(eng, "bm25", lambda: eng.bm25_topk_rows(*csr, 10, lists, list_of=lo))
+    mv, st = _moved(eng, BSTATS, st)
+    assert mv["bm25_rows_scan_calls"] == 0 and mv["bm25_rows_long_launches"] == 1, mv
+    # the error path: a row twice -- ERH_ERR_INVALID, outputs untouched, no counter moved; the handle's class column still works afterwards
+    dir_id = (np.arange(BN) * 4 // BN).astype(np.int16)
+    eng.set_doc_meta(BN, None, dir_id)
+    col = (np.arange(NQ) % 4).astype(np.int16)
+    csr8 = _csr(idx, c["queries"])
+    first = eng.bm25_topk(*csr8, 50, filter_dir=col)
+    for b in range(NQ):
+        oid, osc = _bm25_rank(S[b], np.flatnonzero(dir_id == col[b]), 50)
+        assert np.array_equal(first[0][b, :first[2][b]], oid) and np.array_equal(_bits(first[1][b, :first[2][b]]), _bits(osc)), b
+    st = _stats(eng, BSTATS)
+    rows = lists[2].astype(np.int32).copy()
+    rows[4000] = rows[3999]
+    ptr = np.array([0, len(rows)], np.int64)
+    qi, qt = (np.ascontiguousarray(a, np.int32) for a in csr8)
+    lo8 = np.zeros(NQ, np.int32)
+    ids = np.full((NQ, 3), 77, np.int32)
+    sc = np.full((NQ, 3), 7.5, np.float64)
+    ln = np.full(NQ, 77, np.int32)
+    rc = eng._lib.erh_bm25_topk_rows(eng._h, qi.ctypes.data, qt.ctypes.data, NQ, 3, 1, ptr.ctypes.data, rows.ctypes.data, lo8.ctypes.data,
+                                     ids.ctypes.data, sc.ctypes.data, ln.ctypes.data, 0, 0)
+    assert rc == _lib.ERH_ERR_INVALID and np.all(ids == 77) and np.all(sc == 7.5) and np.all(ln == 77)
+    assert _moved(eng, BSTATS, st)[0] == dict.fromkeys(BSTATS, 0)
+    _same_bytes(first, eng.bm25_topk(*csr8, 50, filter_dir=col))
+    # state restored: a routed call between two filtered calls
+    got = eng.bm25_topk_rows(*csr8, 50, lists[2:4], list_of=(np.arange(NQ) % 2).astype(np.int32))
+    mv, st = _moved(eng, BSTATS, st)
+    assert mv["bm25_rows_scan_calls"] == 1 and mv["bm25_rows_long_launches"] == 0, mv
+    _bm25_check(got, lambda b: S[b], lists[2:4], (np.arange(NQ) % 2).astype(np.int32), 50, "routed, class column set")
+    _same_bytes(first, eng.bm25_topk(*csr8, 50, filter_dir=col))
+    eng.set_doc_meta(BN, None, None)
+    eng.bm25_topk_rows(*csr8, 50, lists[2:4], list_of=(np.arange(NQ) % 2).astype(np.int32))
+    with pytest.raises(_lib.ErhError) as ei:
+        eng.bm25_topk(*csr8, 50, filter_dir=col)
+    assert ei.value.status == _lib.ERH_ERR_STATE
+
+
+def test_bm25_device_outputs_on_a_stream(eng):
+    import torch
+    c = _bm25_corpus(BM25S)
+    idx, S = c["idx"], c["S"]
+    eng.set_bm25(idx)
+    eng.set_doc_meta(BN, None, None)
+    rng = np.random.default_rng(71)
+    lists = [_pick(rng, BN, 12000), _pick(rng, BN, 2049), _pick(rng, BN, 400)]
+    lo = (np.arange(NQ) % 3).astype(np.int32)
+    csr = _csr(idx, c["queries"])
+    host = eng.bm25_topk_rows(*csr, 192, lists, list_of=lo)
+    _bm25_check(host, lambda b: S[b], lists, lo, 192, "host")
+    s2 = torch.cuda.Stream(device=torch.device("cuda", 0))
+    torch.cuda.synchronize()
+    st = _stats(eng, BSTATS)
+    out = eng.bm25_topk_rows(*csr, 192, lists, list_of=lo, device_out=True, stream=s2)
+    eng.sync(s2)
+    mv, st = _moved(eng, BSTATS, st)
+    assert (mv["bm25_rows_scan_calls"], mv["bm25_rows_short_launches"], mv["bm25_rows_long_launches"]) == (1, 1, 0), mv
+    _same_bytes(host, out)
+
+
+# ---- the retrievers get the route for free ------------------------------------------------------------------------------------------------
+def test_hybrid_retriever_on_one_long_list():
+    import zlib
+    from conftest import WhitespaceTokenizer
+    from test_reference_fixtures import DIRS, _fixture, synthetic_text_corpus
+    from easyrag_amd.retrievers import BM25Retriever, HipVectorStore, HybridRetriever, QdrantRetriever
+    from easyrag_amd.schema import TextNode
+
+    class Embedder:
+        def get_query_embedding(self, text, d=128):
+            v = np.random.default_rng(zlib.crc32(text.encode())).standard_normal(d).astype(np.float32)
+            return (v / np.linalg.norm(v)).tolist()
+
+    fx = _fixture()
+    texts, dirs = synthetic_text_corpus(fx, n_docs=5000)
+    nodes = [TextNode(text=t, metadata={"dir": d}, id_=f"n{i}") for i, (t, d) in enumerate(zip(texts, dirs))]
+    emb, tok = Embedder(), WhitespaceTokenizer()
+    vecs = np.asarray([emb.get_query_embedding(f"doc{i}:" + t) for i, t in enumerate(texts)], np.float32)
+    sparse = BM25Retriever.from_defaults(nodes=nodes, tokenizer=tok, similarity_top_k=192, stopwords={""}, bm25_type=0)
+    e = sparse.engine
+    try:
+        store = HipVectorStore(nodes, vecs, engine=e)
+        dense = QdrantRetriever(store, emb, similarity_top_k=288)
+        hy = HybridRetriever(dense, sparse, retrieval_type=3, topk=10)
+        queries = [" ".join(q["tokens"]) for q in fx["queries"]][:24]
+        R = _pick(np.random.default_rng(9), 5000, 3000)
+
+        def pairs(batch):
+            return [[(g.node.node_id, g.score) for g in lst] for lst in batch]
+
+        for route in ("dense", "bm25"):
+            e.set_option(route + "_rows_scan_min_rows", 2049)
+            e.set_option(route + "_rows_scan", 0)
+        want = pairs(hy.retrieve_batch(queries, rows=R, sparse_rows=R))
+        assert e.stat("dense_rows_scan_calls") == 0 and e.stat("bm25_rows_scan_calls") == 0
+        assert e.stat("dense_rows_long_launches") >= 1 and e.stat("bm25_rows_long_launches") >= 1
+        for route in ("dense", "bm25"):
+            e.set_option(route + "_rows_scan", 2)
+        e.reset_stats()
+        got = pairs(hy.retrieve_batch(queries, rows=R, sparse_rows=R))
+        assert e.stat("dense_rows_scan_calls") == 1 and e.stat("bm25_rows_scan_calls") == 1
+        assert e.stat("dense_rows_long_launches") == 0 and e.stat("bm25_rows_long_launches") == 0
+        assert got == want and all(len(g) == 10 for g in got)
+    finally:
+        sparse.close()
+        e.close()
+
+
+# ---- full size, default options: 1M rows, a 500 000-row list shared by 256 queries ----------------------------------------------------------
+def _half_list(n, seed):
+    return np.sort(np.random.default_rng(seed).choice(n, size=n // 2, replace=False)).astype(np.int64)
+
+
+def test_full_size_dense_500k_row_list_shared_by_256_queries(engine):
+    import torch
+    N, D, B, k = 1_000_000, 1024, 256, 100
+    dev = torch.device("cuda", 0)
+    x = synth.dense_corpus_torch(N, D, seed=2, device=dev)
+    q16 = synth.dense_queries_torch(x, B, seed=1000).cpu().numpy()
+    rows = _half_list(N, 5)
+    dir_id = np.zeros(N, np.int16)
+    dir_id[rows] = 1
+    engine.set_dense(x)
+    engine.set_doc_meta(N, None, dir_id)
+    try:
+        assert engine.get_option("dense_rows_scan") == 1 and engine.get_option("dense_rows_scan_min_rows") == 131072
+        want = engine.dense_topk_sets(q16, k, [[1]] * B)
+        engine.reset_stats()
+        got = engine.dense_topk_rows(q16, k, [rows], list_of=np.zeros(B, np.int32))
+        assert engine.stat("dense_rows_calls") == 1 and engine.stat("dense_rows_scan_calls") == 1 and engine.stat("dense_rows_long_launches") == 0
+        assert engine.stat("dense_rows_scan_subqueries") == B and engine.stat("dense_calls") == 0
+        assert np.all(got[2] == k) and np.all(dir_id[got[0]] == 1)
+        _same_bytes(want, got)
+        # one query on a 131072-row list stays on the row-by-row stream
+        engine.dense_topk_rows(q16[:1], k, [rows[:131072]])
+        assert engine.stat("dense_rows_scan_calls") == 1 and engine.stat("dense_rows_long_launches") == 1
+    finally:
+        engine.set_doc_meta(N, None, None)
+
+
+def test_full_size_bm25_500k_row_list_shared_by_256_queries(engine):
+    import torch
+    from easyrag_amd.index import build_bm25_index_from_postings
+    dev = torch.device("cuda", 0)
+    n, vocab, B, k = 1_000_000, 262_144, 256, 100
+    indptr, doc, tf, lens, flat = synth.token_csr_torch(n, vocab, seed=3, device=dev)
+    idx = build_bm25_index_from_postings(indptr, doc, tf, lens, BM25S)
+    engine.set_bm25(idx)
+    rows = _half_list(n, 6)
+    dir_id = np.zeros(n, np.int16)
+    dir_id[rows] = 1
+    engine.set_doc_meta(n, None, dir_id)
+    try:
+        assert engine.get_option("bm25_rows_scan") == 1 and engine.get_option("bm25_rows_scan_min_rows") == 131072
+        qi, qt = queries_to_csr(synth.token_queries(flat, lens, vocab, B, seed=9))
+        want = engine.bm25_topk_sets(qi, qt, k, [[1]] * B)
+        engine.reset_stats()
+        got = engine.bm25_topk_rows(qi, qt, k, [rows], list_of=np.zeros(B, np.int32))
+        assert engine.stat("bm25_rows_calls") == 1 and engine.stat("bm25_rows_scan_calls") == 1 and engine.stat("bm25_rows_long_launches") == 0
+        assert engine.stat("bm25_rows_scan_subqueries") == B and engine.stat("bm25_calls") == 0
+        assert np.all(got[2] > 0)
+        _same_bytes(want, got)
+        engine.bm25_topk_rows(qi[:2], qt[:qi[1]], k, [rows[:131072]])     # one query on a 131072-row list stays on the row-by-row stream
+        assert engine.stat("bm25_rows_scan_calls") == 1 and engine.stat("bm25_rows_long_launches") == 1
+    finally:
+        engine.set_doc_meta(n, None, None)
