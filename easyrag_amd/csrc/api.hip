@@ -1,5 +1,6 @@
 // C ABI of libeasyrag_hip.so (see include/easyrag_hip.h): handle lifetime, options, corpus state (chunk matrix, BM25 indices, metadata),
-// the query entry points and their staging.  Stage orchestration: pipeline_dense.hip / pipeline_bm25.hip; the RCCL exchange: comm.hip.
+// the query entry points and their staging (the two rows entries: rows_entries.hip).  Stage orchestration: pipeline_dense.hip /
+// pipeline_bm25.hip; the RCCL exchange: comm.hip.
 // No CPU compute path lives here.
 #include "../../include/easyrag_hip.h"
 #include "handle.h"
@@ -119,6 +120,143 @@ int dense_sets_check(erh_handle *h, hipStream_t st) {
         h->dense_corrected = false;
     }
     HIPCHK(h, hipStreamSynchronize(st));
+    return ERH_OK;
+}
+
+// ---- what the sets entries below share with the rows entries (rows_entries.hip; declared in handle.h) ----------------------------------------
+static constexpr int kSetsChunk = 8192, kBm25SetsChunk = 8192;     // sub-queries per class-column batch of the dense / sparse sets pipeline
+
+// The argument checks the dense entry points share.  mode < 0: the entry point has none, and refuses k < 1 as unsupported
+// (erh_dense_topk_rows).
+int check_dense_args(erh_handle *h, const char *who, const void *q, bool outs, int B, int k, int q_dtype, int mode) {
+    const std::string w(who);
+    if (!h->X.p || h->N <= 0) return h->fail(ERH_ERR_STATE, (w + " before erh_set_dense").c_str());
+    if (!q || !outs || B <= 0 || (mode >= 0 && k <= 0)) return h->fail(ERH_ERR_INVALID, (w + ": null pointer or non-positive B/k").c_str());
+    if (q_dtype != ERH_F16 && q_dtype != ERH_F32) return h->fail(ERH_ERR_INVALID, (w + ": q_dtype").c_str());
+    if (mode >= 0 && mode != ERH_DENSE_EXACT && mode != ERH_DENSE_FAST) return h->fail(ERH_ERR_INVALID, (w + ": mode").c_str());
+    if (k < 1 || k > 768) return h->fail(ERH_ERR_UNSUPPORTED, (w + (mode >= 0 ? ": k > 768" : ": k outside [1, 768]")).c_str());
+    return ERH_OK;
+}
+
+// The query CSR of erh_bm25_topk_sets and erh_bm25_topk_rows, as erh_bm25_topk takes it: monotone from 0, term ids inside [0, V).
+int check_bm25_queries(erh_handle *h, const char *who, const int32_t *q_indptr, const int32_t *q_tok, int B, int64_t V) {
+    const std::string w(who);
+    if (q_indptr[0] != 0) return h->fail(ERH_ERR_INVALID, (w + ": q_indptr[0] must be 0").c_str());
+    for (int b = 0; b < B; ++b)
+        if (q_indptr[b + 1] < q_indptr[b]) return h->fail(ERH_ERR_INVALID, (w + ": q_indptr must be non-decreasing").c_str());
+    const int nt = q_indptr[B];
+    if (nt > 0 && !q_tok) return h->fail(ERH_ERR_INVALID, (w + ": null q_tok").c_str());
+    for (int i = 0; i < nt; ++i)
+        if (q_tok[i] < 0 || q_tok[i] >= V) return h->fail(ERH_ERR_INVALID, (w + ": query term id out of range").c_str());
+    return ERH_OK;
+}
+
+// The sub-query batch of a set-filtered dense call on device buffers, behind validation: one upload of its tables, the sub-queries' rows
+// gathered from the query block `qd` (device), the class-column pipeline per chunk, the merge into d_ids / d_sc / d_len [B x k], and the
+// record erh_dense_check -> dense_sets_check finishes it by.  Shared by erh_dense_topk_sets and the scan route of erh_dense_topk_rows, which
+// runs it on a call-local class column (rows_entries.hip: CallClasses).
+int dense_sets_run(erh_handle *h, const void *qd, int q_dtype, int normalize_q, int B, int k, const std::vector<int32_t> &sub_ptr,
+                          const std::vector<int32_t> &src, const std::vector<int16_t> &cls, int mode, int32_t *d_ids, double *d_sc,
+                          int32_t *d_len, hipStream_t st) {
+    const int n_sub = (int)src.size();
+    TableBuilder tab;                                  // (sub_ptr first: dense_sets_check reads it at the head of s_tab)
+    const auto s_ptr = tab.add(sub_ptr);
+    const auto s_src = tab.add(src);
+    const auto s_cls = tab.add(cls);
+    HIPCHK(h, tab.upload(h->s_tab, st));
+    HIPCHK(h, hipStreamSynchronize(st));               // (the table is pageable memory of this scope)
+    const int32_t *d_ptr = tab.at(s_ptr), *d_src = tab.at(s_src);
+    const int16_t *d_cls = tab.at(s_cls);
+    erh_handle::DenseSets &S = h->sets;
+    S = erh_handle::DenseSets();
+    S.B = B; S.k = k; S.n_sub = n_sub; S.d_ids = d_ids; S.d_sc = d_sc; S.d_len = d_len;
+    if (n_sub > 0) {
+        const size_t row_bytes = (size_t)h->d * (q_dtype == ERH_F16 ? 2 : 4);
+        HIPCHK(h, h->s_q.ensure((size_t)n_sub * row_bytes));
+        HIPCHK(h, h->s_ids.ensure((size_t)n_sub * k * 4));
+        HIPCHK(h, h->s_sc.ensure((size_t)n_sub * k * 8));
+        HIPCHK(h, h->s_len.ensure((size_t)n_sub * 4));
+        HIPCHK(h, erh::launch_gather_query_rows(qd, d_src, n_sub, (int)row_bytes, h->s_q.p, st));
+        for (int c0 = 0; c0 < n_sub; c0 += kSetsChunk) {
+            const int nb = std::min(kSetsChunk, n_sub - c0);
+            if (c0 > 0) {                              // the previous chunk must be final before this one reuses the work space
+                const int rc = dense_check_flags(h, st);
+                if (rc != ERH_OK) return rc;
+                S.acc_maxerr = std::max(S.acc_maxerr, h->diag_maxerr); S.acc_uncert += h->diag_uncert; S.acc_exhaustive += h->diag_exhaustive;
+            }
+            bool filtered = false;
+            for (int i = 0; i < nb; ++i) filtered = filtered || cls[(size_t)c0 + i] >= 0;
+            const int rc = dense_topk_routed(h, h->s_q.as<char>() + (size_t)c0 * row_bytes, q_dtype, normalize_q, nb, k,
+                                             filtered ? cls.data() + c0 : nullptr, filtered ? d_cls + c0 : nullptr, mode,
+                                             h->s_ids.as<int32_t>() + (size_t)c0 * k, h->s_sc.as<double>() + (size_t)c0 * k,
+                                             h->s_len.as<int32_t>() + c0, st);
+            if (rc != ERH_OK) return rc;
+        }
+    }
+    HIPCHK(h, erh::launch_dense_set_merge(h->s_ids.as<int32_t>(), h->s_sc.as<double>(), h->s_len.as<int32_t>(), d_ptr, B, k,
+                                          d_ids, d_sc, d_len, st));
+    S.on = true;
+    return ERH_OK;
+}
+
+// The sub-query batch of a set-filtered BM25 call behind validation: chunk after chunk through upload_bm25_queries + bm25_topk_dev into
+// bs_ids / bs_sc / bs_len, then the merge into d_ids / d_sc / d_len [B x k].  Shared by erh_bm25_topk_sets and the scan route of
+// erh_bm25_topk_rows, which runs it on a call-local class column (CallClasses).  The caller has checked that a chunk's tokens fit 32 bits
+// (bm25_sets_tokens_fit) and counts its own stats.
+bool bm25_sets_tokens_fit(const int32_t *q_indptr, const std::vector<int32_t> &src) {
+    const int n_sub = (int)src.size();
+    for (int c0 = 0; c0 < n_sub; c0 += kBm25SetsChunk) {             // a chunk's query CSR has 32-bit offsets
+        int64_t toks = 0;
+        for (int i = c0; i < std::min(n_sub, c0 + kBm25SetsChunk); ++i) toks += q_indptr[src[i] + 1] - q_indptr[src[i]];
+        if (toks > 2147483647LL) return false;
+    }
+    return true;
+}
+
+int bm25_sets_run(erh_handle *h, const char *who, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
+                         const std::vector<int32_t> &sub_ptr, const std::vector<int32_t> &src, const std::vector<int16_t> &cls,
+                         int32_t *d_ids, double *d_sc, int32_t *d_len, hipStream_t st) {
+    const Bm25State &S = h->bm[h->cur];
+    const int n_sub = (int)src.size();
+    // buffers first: a call that cannot have them enqueues nothing
+    {
+        hipError_t e = h->bs_tab.ensure(((size_t)B + 1) * 4);
+        if (e == hipSuccess && n_sub > 0) e = h->bs_ids.ensure((size_t)n_sub * k * 4);
+        if (e == hipSuccess && n_sub > 0) e = h->bs_sc.ensure((size_t)n_sub * k * 8);
+        if (e == hipSuccess && n_sub > 0) e = h->bs_len.ensure((size_t)n_sub * 4);
+        if (e != hipSuccess) { (void)hipGetLastError(); return h->fail(ERH_ERR_NOMEM, (std::string(who) + ": work space").c_str(), e); }
+    }
+    HIPCHK(h, hipMemcpyAsync(h->bs_tab.p, sub_ptr.data(), ((size_t)B + 1) * 4, hipMemcpyHostToDevice, st));
+    // (`sub_ptr` is pageable memory of the caller's scope -- and whatever was enqueued in front of this call has now read the query staging
+    // (qpack_host) that the first chunk is about to overwrite)
+    HIPCHK(h, hipStreamSynchronize(st));
+    std::vector<int32_t> c_ptr, c_tok;
+    for (int c0 = 0; c0 < n_sub; c0 += kBm25SetsChunk) {
+        const int nb = std::min(kBm25SetsChunk, n_sub - c0);
+        c_ptr.assign((size_t)nb + 1, 0);
+        c_tok.clear();
+        bool filtered = false;
+        for (int i = 0; i < nb; ++i) {
+            const int b = src[(size_t)c0 + i];
+            if (q_indptr[b + 1] > q_indptr[b]) c_tok.insert(c_tok.end(), q_tok + q_indptr[b], q_tok + q_indptr[b + 1]);
+            c_ptr[(size_t)i + 1] = (int32_t)c_tok.size();
+            filtered = filtered || cls[(size_t)c0 + i] >= 0;
+        }
+        // the upload below rewrites the host staging of the query CSR: the previous chunk's copy must have read it
+        if (c0 > 0) HIPCHK(h, hipStreamSynchronize(st));
+        double bytes = 0;
+        int max_qlen = 0;
+        const int16_t *filt = nullptr;
+        int rc = upload_bm25_queries(h, c_ptr.data(), c_tok.data(), nb, st, S.host_indptr, &bytes, &max_qlen,
+                                     filtered ? cls.data() + c0 : nullptr, &filt);
+        if (rc != ERH_OK) return rc;
+        rc = bm25_topk_dev(h, h->qptr, h->qtok, nb, k, filt, h->bs_ids.as<int32_t>() + (size_t)c0 * k, h->bs_sc.as<double>() + (size_t)c0 * k,
+                           h->bs_len.as<int32_t>() + c0, bytes, max_qlen, st);
+        if (rc != ERH_OK) return rc;
+    }
+    { ProfScope ps(h, st, ERH_K_BM25_MERGE, (double)n_sub * k * 12, 0);
+      HIPCHK(h, erh::launch_bm25_set_merge(h->bs_ids.as<int32_t>(), h->bs_sc.as<double>(), h->bs_len.as<int32_t>(), h->bs_tab.as<int32_t>(), B, k,
+                                           d_ids, d_sc, d_len, st)); }
     return ERH_OK;
 }
 
@@ -906,47 +1044,6 @@ static int stage_query_block(erh_handle *h, const void *q, int q_dtype, int q_is
     return ERH_OK;
 }
 
-// Where a call's kernels write its top-k lists: the caller's rows when they are on the device, else staging buffers of the handle
-// (o_* unless the call names its own) that finish() copies to the caller's host rows.
-struct HostOut {
-    erh_handle *h;
-    int32_t *out_ids; double *out_sc; int32_t *out_len;             // the caller's rows
-    bool host;
-    int B, k;
-    DevBuf *b_ids = &h->o_ids, *b_sc = &h->o_sc, *b_len = &h->o_len;   // the staging buffers (erh_dense_topk_rows points them at its own)
-    int32_t *d_ids; double *d_sc; int32_t *d_len;                   // where the kernels write
-    HostOut(erh_handle *h_, int32_t *ids, double *sc, int32_t *len, int out_is_device, int B_, int k_)
-        : h(h_), out_ids(ids), out_sc(sc), out_len(len), host(!out_is_device), B(B_), k(k_), d_ids(ids), d_sc(sc), d_len(len) {}
-    hipError_t ensure() {                                           // before the first kernel that writes the lists
-        if (!host) return hipSuccess;
-        hipError_t e = b_ids->ensure((size_t)B * k * 4);
-        if (e == hipSuccess) e = b_sc->ensure((size_t)B * k * 8);
-        if (e == hipSuccess) e = b_len->ensure((size_t)B * 4);
-        d_ids = b_ids->as<int32_t>(); d_sc = b_sc->as<double>(); d_len = b_len->as<int32_t>();
-        return e;
-    }
-    int finish(hipStream_t st) {                                    // the call's last step: lists to the host (synchronises), or nothing
-        if (!host) return ERH_OK;
-        HIPCHK(h, hipMemcpyAsync(out_ids, d_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(out_sc, d_sc, (size_t)B * k * 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipMemcpyAsync(out_len, d_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-        return ERH_OK;
-    }
-};
-
-// The argument checks the three dense entry points share.  mode < 0: the entry point has none, and refuses k < 1 as unsupported
-// (erh_dense_topk_rows).
-static int check_dense_args(erh_handle *h, const char *who, const void *q, bool outs, int B, int k, int q_dtype, int mode) {
-    const std::string w(who);
-    if (!h->X.p || h->N <= 0) return h->fail(ERH_ERR_STATE, (w + " before erh_set_dense").c_str());
-    if (!q || !outs || B <= 0 || (mode >= 0 && k <= 0)) return h->fail(ERH_ERR_INVALID, (w + ": null pointer or non-positive B/k").c_str());
-    if (q_dtype != ERH_F16 && q_dtype != ERH_F32) return h->fail(ERH_ERR_INVALID, (w + ": q_dtype").c_str());
-    if (mode >= 0 && mode != ERH_DENSE_EXACT && mode != ERH_DENSE_FAST) return h->fail(ERH_ERR_INVALID, (w + ": mode").c_str());
-    if (k < 1 || k > 768) return h->fail(ERH_ERR_UNSUPPORTED, (w + (mode >= 0 ? ": k > 768" : ": k outside [1, 768]")).c_str());
-    return ERH_OK;
-}
-
 int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
                    int B, int k, const int16_t *filter_dir, int mode,
                    int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
@@ -975,7 +1072,6 @@ int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, i
 // kSetsChunk sub-queries when the batch is larger: every chunk but the last is checked before the next one reuses the work space), then
 // one merge launch (dense_sets.hip) builds each query's list from its sub-lists.  An unfiltered query ({-1}) is one sub-query without a
 // class, an empty set none.  erh_dense_check -> dense_sets_check: the sub-queries' flag words, and the merge again if they changed a list.
-static constexpr int kSetsChunk = 8192;
 
 // The class-set CSR of the two sets entries (erh_dense_topk_sets, erh_bm25_topk_sets): monotone from 0, classes >= 0 (32767 = matches
 // nothing) and distinct within a set, or the set {-1} alone; a set that names a class needs a class column over all n_docs documents.
@@ -1022,58 +1118,6 @@ static void expand_class_sets(const erh_handle *h, const int32_t *set_ptr, const
     }
 }
 
-// The sub-query batch of a set-filtered dense call on device buffers, behind validation: one upload of its tables, the sub-queries' rows
-// gathered from the query block `qd` (device), the class-column pipeline per chunk, the merge into d_ids / d_sc / d_len [B x k], and the
-// record erh_dense_check -> dense_sets_check finishes it by.  Shared by erh_dense_topk_sets and the scan route of erh_dense_topk_rows, which
-// runs it on a call-local class column (CallClasses below).
-static int dense_sets_run(erh_handle *h, const void *qd, int q_dtype, int normalize_q, int B, int k, const std::vector<int32_t> &sub_ptr,
-                          const std::vector<int32_t> &src, const std::vector<int16_t> &cls, int mode, int32_t *d_ids, double *d_sc,
-                          int32_t *d_len, hipStream_t st) {
-    const int n_sub = (int)src.size();
-    const size_t off_src = ((size_t)B + 1) * 4, off_cls = off_src + (size_t)n_sub * 4;
-    {
-        std::vector<char> tab(off_cls + (size_t)n_sub * 2);
-        memcpy(tab.data(), sub_ptr.data(), off_src);
-        if (n_sub) { memcpy(tab.data() + off_src, src.data(), (size_t)n_sub * 4); memcpy(tab.data() + off_cls, cls.data(), (size_t)n_sub * 2); }
-        HIPCHK(h, h->s_tab.ensure(tab.size()));
-        HIPCHK(h, hipMemcpyAsync(h->s_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipStreamSynchronize(st));           // (`tab` is pageable memory of this scope)
-    }
-    const int32_t *d_ptr = h->s_tab.as<int32_t>();
-    const int32_t *d_src = reinterpret_cast<const int32_t *>(h->s_tab.as<char>() + off_src);
-    const int16_t *d_cls = reinterpret_cast<const int16_t *>(h->s_tab.as<char>() + off_cls);
-    erh_handle::DenseSets &S = h->sets;
-    S = erh_handle::DenseSets();
-    S.B = B; S.k = k; S.n_sub = n_sub; S.d_ids = d_ids; S.d_sc = d_sc; S.d_len = d_len;
-    if (n_sub > 0) {
-        const size_t row_bytes = (size_t)h->d * (q_dtype == ERH_F16 ? 2 : 4);
-        HIPCHK(h, h->s_q.ensure((size_t)n_sub * row_bytes));
-        HIPCHK(h, h->s_ids.ensure((size_t)n_sub * k * 4));
-        HIPCHK(h, h->s_sc.ensure((size_t)n_sub * k * 8));
-        HIPCHK(h, h->s_len.ensure((size_t)n_sub * 4));
-        HIPCHK(h, erh::launch_gather_query_rows(qd, d_src, n_sub, (int)row_bytes, h->s_q.p, st));
-        for (int c0 = 0; c0 < n_sub; c0 += kSetsChunk) {
-            const int nb = std::min(kSetsChunk, n_sub - c0);
-            if (c0 > 0) {                              // the previous chunk must be final before this one reuses the work space
-                const int rc = dense_check_flags(h, st);
-                if (rc != ERH_OK) return rc;
-                S.acc_maxerr = std::max(S.acc_maxerr, h->diag_maxerr); S.acc_uncert += h->diag_uncert; S.acc_exhaustive += h->diag_exhaustive;
-            }
-            bool filtered = false;
-            for (int i = 0; i < nb; ++i) filtered = filtered || cls[(size_t)c0 + i] >= 0;
-            const int rc = dense_topk_routed(h, h->s_q.as<char>() + (size_t)c0 * row_bytes, q_dtype, normalize_q, nb, k,
-                                             filtered ? cls.data() + c0 : nullptr, filtered ? d_cls + c0 : nullptr, mode,
-                                             h->s_ids.as<int32_t>() + (size_t)c0 * k, h->s_sc.as<double>() + (size_t)c0 * k,
-                                             h->s_len.as<int32_t>() + c0, st);
-            if (rc != ERH_OK) return rc;
-        }
-    }
-    HIPCHK(h, erh::launch_dense_set_merge(h->s_ids.as<int32_t>(), h->s_sc.as<double>(), h->s_len.as<int32_t>(), d_ptr, B, k,
-                                          d_ids, d_sc, d_len, st));
-    S.on = true;
-    return ERH_OK;
-}
-
 int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
                         int B, int k, const int32_t *set_ptr, const int16_t *set_cls, int mode,
                         int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
@@ -1101,380 +1145,6 @@ int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_devi
     return rc == ERH_OK ? out.finish(st) : rc;
 }
 
-// ---- the scan route of the rows entries (DESIGN K11; kernels: rows_classes.hip) -----------------------------------------------------------
-// The long lists of a rows call become a call-local class column; the call's queries on those lists run through the sets pipelines above
-// on that column, installed in place of the handle's own class state for the duration of the call.
-
-// Which lists of a call may take the scan route: named by a query, at least min_rows rows and longer than the short shape -- at most
-// kRowsClassLists of them (more: none, the call keeps today's shapes).  bit[l]: the list's signature bit, -1 = not routed.
-struct RowsScanPlan {
-    std::vector<int32_t> bit;
-    std::vector<int64_t> routed;             // {first entry, length} per routed list: what rows_sig_kernel reads
-    std::vector<int32_t> n_q;                // queries per list
-    int n_routed = 0, n_queries = 0, max_cells = 0, slots = 0;
-    int64_t max_len = 0;
-    void clear() { bit.assign(bit.size(), -1); routed.clear(); n_routed = n_queries = 0; }
-};
-static void rows_scan_candidates(int opt, int64_t min_rows, int n_lists, const int64_t *list_ptr, const int32_t *list_of, int B, int64_t N,
-                                 RowsScanPlan *P) {
-    P->bit.assign((size_t)n_lists, -1);
-    P->n_q.assign((size_t)n_lists, 0);
-    if (opt == 0 || N > 2147483647LL) return;
-    for (int b = 0; b < B; ++b) if (list_of[b] >= 0) P->n_q[(size_t)list_of[b]] += 1;
-    int n = 0;
-    for (int l = 0; l < n_lists; ++l) {
-        const int64_t len = list_ptr[l + 1] - list_ptr[l];
-        if (P->n_q[l] > 0 && len >= min_rows && len > erh::kDenseRowsShortMax) ++n;
-    }
-    if (n == 0 || n > erh::kRowsClassLists) return;
-    int64_t entries = 0;
-    for (int l = 0; l < n_lists; ++l) {
-        const int64_t len = list_ptr[l + 1] - list_ptr[l];
-        if (!(P->n_q[l] > 0 && len >= min_rows && len > erh::kDenseRowsShortMax)) continue;
-        P->bit[l] = P->n_routed++;
-        P->routed.push_back(list_ptr[l]); P->routed.push_back(len);
-        P->n_queries += P->n_q[l];
-        P->max_len = std::max(P->max_len, len);
-        entries += len;
-    }
-    // cells are non-empty and distinct: no more than entries, nor than the non-zero signatures of n_routed bits; one more than the column
-    // can number is enough to see that there are too many
-    int64_t bound = std::min<int64_t>(entries, (int64_t)erh::kRowsClassMax + 1);
-    if (P->n_routed < 16) bound = std::min<int64_t>(bound, ((int64_t)1 << P->n_routed) - 1);
-    P->max_cells = (int)bound;
-    P->slots = erh::rows_classes_slots(bound);
-}
-
-// The host step: cells (signatures) -> the class sets of the call's queries.  bit_of[b]: the signature bit of query b's list, -1 = the query
-// is not on the scan route (no sub-query).  Query b's set is every cell whose signature has its bit, in cell order.  False: the call keeps
-// the row-by-row shapes (more lists than signature bits, more cells than an int16 column numbers).  Needs no device.
-static bool rows_class_sets(const uint64_t *sig, int n_cells, int n_routed, const int32_t *bit_of, int B, std::vector<int32_t> &sub_ptr,
-                            std::vector<int32_t> &src, std::vector<int16_t> &cls) {
-    sub_ptr.assign((size_t)B + 1, 0);
-    src.clear(); cls.clear();
-    if (n_routed < 0 || n_routed > erh::kRowsClassLists || n_cells < 0 || n_cells > erh::kRowsClassMax) return false;
-    // cells of every bit once, then every query copies its bit's
-    std::vector<std::vector<int16_t>> of_bit((size_t)n_routed);
-    for (int c = 0; c < n_cells; ++c)
-        for (int l = 0; l < n_routed; ++l)
-            if ((sig[c] >> l) & 1ull) of_bit[(size_t)l].push_back((int16_t)c);
-    for (int b = 0; b < B; ++b) {
-        const int l = bit_of[b];
-        if (l >= 0 && l < n_routed)
-            for (int16_t c : of_bit[(size_t)l]) { src.push_back(b); cls.push_back(c); }
-        sub_ptr[(size_t)b + 1] = (int32_t)src.size();
-    }
-    return true;
-}
-
-// Buffers of the scan route (before anything is enqueued), then: signatures, cells, column, and the cells read back (one copy; synchronises).
-static hipError_t rows_classes_ensure(erh_handle::RowsClasses &rc, const RowsScanPlan &P, int64_t N) {
-    hipError_t e = rc.sig.ensure((size_t)N * 8);
-    if (e == hipSuccess) e = rc.cls.ensure((size_t)N * 2);
-    if (e == hipSuccess) e = rc.table.ensure(erh::rows_classes_table_bytes(P.slots, P.max_cells));
-    return e;
-}
-// 0: *cells / *n_cells hold the call's cells; 1: too many cells for the column -- today's shapes; < 0: an error
-static int rows_classes_build(erh_handle *h, erh_handle::RowsClasses &rc, const RowsScanPlan &P, const int32_t *d_rows, const int64_t *d_routed,
-                              int64_t N, int prof_class, hipStream_t st, const erh::ErhRowsCell **cells, int *n_cells) {
-    { ProfScope ps(h, st, prof_class, (double)N * 26.0, 0);             // (each row: its word cleared, read twice, its class written)
-      HIPCHK(h, erh::launch_rows_classes(d_rows, d_routed, P.n_routed, P.max_len, N, P.slots, P.max_cells, rc.sig.as<unsigned long long>(),
-                                         rc.table.p, rc.cls.as<int16_t>(), st)); }
-    const size_t bytes = 16 + (size_t)P.max_cells * sizeof(erh::ErhRowsCell);
-    rc.cells_host.resize(bytes);
-    HIPCHK(h, hipMemcpyAsync(rc.cells_host.data(), rc.table.p, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    uint32_t hdr[4];
-    memcpy(hdr, rc.cells_host.data(), 16);
-    if (hdr[1] != 0u || hdr[0] > (uint32_t)erh::kRowsClassMax || hdr[0] > (uint32_t)P.max_cells) return 1;
-    *cells = reinterpret_cast<const erh::ErhRowsCell *>(rc.cells_host.data() + 16);
-    *n_cells = (int)hdr[0];
-    return 0;
-}
-
-// A call that the scan route hands back keeps its uploaded row ids (device to device, `total` x 4 bytes) for the pass that answers it on the
-// row-by-row shapes; that pass's own table may move or overwrite the first one.  Synchronises: the first table may be freed next.
-static int rows_keep(erh_handle *h, erh_handle::RowsClasses &rc, const int32_t *d_rows, int64_t total, hipStream_t st, const int32_t **kept) {
-    hipError_t e = rc.keep.ensure((size_t)std::max<int64_t>(total, 1) * 4);
-    if (e != hipSuccess) { (void)hipGetLastError(); return h->fail(ERH_ERR_NOMEM, "rows call: work space", e); }
-    if (total > 0) HIPCHK(h, hipMemcpyAsync(rc.keep.p, d_rows, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    *kept = rc.keep.as<int32_t>();
-    return ERH_OK;
-}
-
-// The class state of a handle -- everything it derives from erh_set_doc_meta's dir_id -- exchanged with a call-local column for the
-// lifetime of this object: the column itself, its copy by stored position, the classes' row ranges and counts.  Dense dir blocks are off
-// meanwhile (they would gather up to the whole matrix per call): the call scans through the filter column.  The destructor puts the
-// handle's own state back, on every path; the call-local buffers return to `rc` for the next call.
-struct CallClasses {
-    erh_handle *h;
-    erh_handle::RowsClasses &rc;
-    bool on = false, has_dir = false, dir_pos_valid = false;
-    int64_t Nmeta = 0;
-    int dir_rng_n = 0, dense_dir_blocks = 0;
-    std::vector<int32_t> lo, hi, cnt, order;
-    std::vector<int64_t> off;
-    erh_handle::DenseBlocks blocks;
-    CallClasses(erh_handle *h_, erh_handle::RowsClasses &rc_) : h(h_), rc(rc_) {}
-    CallClasses(const CallClasses &) = delete;
-    CallClasses &operator=(const CallClasses &) = delete;
-    void exchange() {
-        std::swap(h->dir_id, rc.cls); std::swap(h->dir_pos, rc.pos); std::swap(h->dir_rng, rc.rng);
-        std::swap(h->dir_lo_h, lo); std::swap(h->dir_hi_h, hi); std::swap(h->dir_cnt_h, cnt); std::swap(h->dir_order_h, order);
-        std::swap(h->dir_off_h, off); std::swap(h->blocks, blocks);
-    }
-    // with_ranges: the cells' row ranges go up for bm25_dir_range (the copy is ordered in front of the call's scans on `st`)
-    int enter(const erh::ErhRowsCell *cells, int n_cells, int64_t N, bool with_ranges, hipStream_t st) {
-        if (with_ranges) {
-            rc.rng_host.resize((size_t)n_cells * 2);
-            for (int c = 0; c < n_cells; ++c) { rc.rng_host[2 * (size_t)c] = cells[c].lo; rc.rng_host[2 * (size_t)c + 1] = cells[c].hi; }
-            HIPCHK(h, rc.rng.ensure((size_t)n_cells * 8));
-            HIPCHK(h, hipMemcpyAsync(rc.rng.p, rc.rng_host.data(), (size_t)n_cells * 8, hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipStreamSynchronize(st));             // (rng_host is pageable and reused by the next routed call, whatever its stream;
-                                                             //  8 bytes per cell, and the stream is idle: the cells were just read back)
-        }
-        has_dir = h->has_dir; dir_pos_valid = h->dir_pos_valid; Nmeta = h->Nmeta; dir_rng_n = h->dir_rng_n;
-        dense_dir_blocks = h->opt_dense_dir_blocks;
-        exchange();
-        on = true;
-        h->has_dir = true; h->dir_pos_valid = false; h->Nmeta = N; h->dir_rng_n = with_ranges ? n_cells : 0;
-        h->opt_dense_dir_blocks = 0;
-        h->dir_lo_h.resize((size_t)n_cells); h->dir_hi_h.resize((size_t)n_cells); h->dir_cnt_h.resize((size_t)n_cells);
-        for (int c = 0; c < n_cells; ++c) { h->dir_lo_h[c] = cells[c].lo; h->dir_hi_h[c] = cells[c].hi; h->dir_cnt_h[c] = cells[c].cnt; }
-        return ERH_OK;
-    }
-    ~CallClasses() {
-        if (!on) return;
-        exchange();
-        h->has_dir = has_dir; h->dir_pos_valid = dir_pos_valid; h->Nmeta = Nmeta; h->dir_rng_n = dir_rng_n;
-        h->opt_dense_dir_blocks = dense_dir_blocks;
-    }
-};
-
-static constexpr int kBm25SetsChunk = 8192;
-static bool bm25_sets_tokens_fit(const int32_t *q_indptr, const std::vector<int32_t> &src);
-static int bm25_sets_run(erh_handle *h, const char *who, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
-                         const std::vector<int32_t> &sub_ptr, const std::vector<int32_t> &src, const std::vector<int16_t> &cls,
-                         int32_t *d_ids, double *d_sc, int32_t *d_len, hipStream_t st);
-
-// Explicit row lists (dense_rows.hip).  The call keeps to buffers of its own (rw_*) and touches neither the flag words nor the record of the
-// last scan-route call: it has no threshold to verify, so nothing of it is left for erh_dense_check, and a device-output dense call that is
-// still waiting for its check finds everything as it left it.  Queries are prepared by the same kernel as on every other route (the fp16
-// values the scores are defined on).  Lists of at most kDenseRowsShortMax rows: one launch for all their queries; longer ones: score + select
-// launches per chunk of queries whose score spans fit the work space -- chunks follow each other on the stream, which is what orders the reuse
-// of the span buffer; the work-item tables of the whole call go up once.
-//   The scan route (DESIGN K11): the call's long lists that the work rule sends there (options dense_rows_scan, dense_rows_scan_min_rows) become
-// a call-local class column (rows_classes.hip) and their queries one set-filtered batch of the scan pipeline (dense_sets_run) on that column,
-// installed for the call by a CallClasses guard.  That batch is checked INSIDE the call (its flag words and exhaustive rounds read the
-// column), so the entry's contract stands: no erh_dense_check, host outputs final on return, device outputs after erh_sync.  The merge
-// writes every row of the batch (an empty list for the queries that are not on the route); the short and long shapes then overwrite theirs.
-// While a device-output scan-route call waits for its check (check_pending) the scan route is off: it would clobber that call's work space.
-// kept_rows: the call that the scan route handed back (too many cells, or the rule said no once the cells were known) -- the lists were
-// validated and uploaded by the first pass, which kept the row ids on the device (RowsClasses::keep): this pass neither checks nor uploads
-// them again, so a hand-back costs the classification and the small tables, not megabytes of row ids a second time.
-static bool dense_rows_scan_pays(const erh_handle *h, const RowsScanPlan &P, int64_t n_sub, int64_t n_sub_small) {
-    // today's work: every routed list is loaded once per group of kDenseRowsGroup queries; the scan's: N rows x the sub-queries' columns,
-    // a scan narrower than the ridge counted as the ridge (HBM-bound).  One constant (gain) relates the two.  n_sub_small of the n_sub
-    // sub-queries are on cells so small that the seed prefix holds fewer than k of their rows (dense_rows_cell_is_small): the pipeline has
-    // no threshold to prune them with, and each costs dense_rows_scan_small_cell ordinary sub-queries.
-    double today = 0;
-    for (size_t l = 0; l < P.bit.size(); ++l)
-        if (P.bit[l] >= 0) today += (double)((P.n_q[l] + erh::kDenseRowsGroup - 1) / erh::kDenseRowsGroup) * (double)P.routed[2 * (size_t)P.bit[l] + 1];
-    const double cols = (double)(n_sub - n_sub_small) + (double)n_sub_small * (double)h->opt_dense_rows_scan_small_cell;
-    const double scan = (double)h->N * std::max(cols, (double)h->opt_route_ridge);
-    return today * (double)h->opt_dense_rows_scan_gain > scan;
-}
-static bool dense_rows_cell_is_small(const erh_handle *h, int64_t cell_rows, int k) {
-    const int64_t n0 = std::min<int64_t>(h->opt_n0, h->N);               // the seed prefix is an even sample: cell_rows * n0 / N of them are the cell's
-    return (double)cell_rows * (double)n0 < (double)k * (double)h->N;
-}
-
-static int dense_topk_rows_impl(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q, int B, int k,
-                                int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
-                                int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream, const int32_t *kept_rows) {
-    const bool allow_scan = kept_rows == nullptr;
-    const int rc = check_dense_args(h, "erh_dense_topk_rows", q, out_ids && out_scores && out_len && list_of, B, k, q_dtype, -1);
-    if (rc != ERH_OK) return rc;
-    if (n_lists < 0 || (n_lists > 0 && !list_ptr)) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: negative n_lists or null list_ptr");
-    const int64_t N = h->N;
-    const int d = h->d;
-    // the lists: a monotone CSR from 0, every list strictly ascending inside [0, N)
-    int64_t total = 0;
-    if (n_lists > 0) {
-        if (list_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: list_ptr[0] != 0");
-        for (int l = 0; l < n_lists; ++l)
-            if (list_ptr[l + 1] < list_ptr[l]) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: list_ptr decreases");
-        total = list_ptr[n_lists];
-        if (total > 0 && !list_rows) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: null list_rows");
-        for (int l = 0; l < n_lists && allow_scan; ++l)
-            for (int64_t i = list_ptr[l]; i < list_ptr[l + 1]; ++i) {
-                const int32_t r = list_rows[i];
-                if (r < 0 || (int64_t)r >= N) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: row outside [0, N)");
-                if (i > list_ptr[l] && r <= list_rows[i - 1]) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: rows of a list must be strictly ascending");
-            }
-    }
-    for (int b = 0; b < B; ++b)
-        if (list_of[b] < -1 || list_of[b] >= n_lists) return h->fail(ERH_ERR_INVALID, "erh_dense_topk_rows: list_of outside [-1, n_lists)");
-    auto len_of = [&](int b) -> int64_t { const int l = list_of[b]; return l < 0 ? 0 : list_ptr[l + 1] - list_ptr[l]; };
-    // the scan route's lists first; then the shapes: the short one for every other query whose list fits the LDS sort, the long one for the
-    // rest, grouped by list
-    // (decided from the list lengths alone, before any routing: the status of a call does not depend on the rule)
-    for (int b = 0; b < B; ++b)
-        if (len_of(b) > erh::kDenseRowsShortMax && erh::dense_rows_score_lds(d) > 128 * 1024)
-            return h->fail(ERH_ERR_UNSUPPORTED, "erh_dense_topk_rows: d too large for lists longer than 2048 rows");
-    RowsScanPlan SP;
-    const int scan_opt = (allow_scan && !h->check_pending) ? h->opt_dense_rows_scan : 0;
-    rows_scan_candidates(scan_opt, h->opt_dense_rows_scan_min_rows, n_lists, list_ptr, list_of, B, N, &SP);
-    if (SP.n_routed && scan_opt == 1 && !dense_rows_scan_pays(h, SP, SP.n_queries, 0)) SP.clear();   // (a query is at least one sub-query)
-    std::vector<int32_t> q_short, q_long, bit_of((size_t)B, -1);
-    for (int b = 0; b < B; ++b) {
-        if (list_of[b] >= 0 && SP.bit[(size_t)list_of[b]] >= 0) bit_of[(size_t)b] = SP.bit[(size_t)list_of[b]];
-        else (len_of(b) <= erh::kDenseRowsShortMax ? q_short : q_long).push_back(b);
-    }
-    std::stable_sort(q_long.begin(), q_long.end(), [&](int32_t a, int32_t b) { return list_of[a] < list_of[b]; });
-    // chunks of long queries (whole list groups of <= kDenseRowsGroup where they fit) whose spans fit the work space; span offsets are relative
-    // to the chunk
-    const int64_t ws_doubles = std::max<int64_t>((h->opt_rows_ws_mb << 20) / 8, N);
-    struct Chunk { int q0, q1; int64_t item0, item1, doubles; };
-    std::vector<Chunk> chunks;
-    std::vector<int64_t> span_off((size_t)B, 0);
-    std::vector<erh::ErhRowsItem> items;
-    {
-        size_t i = 0;
-        Chunk c{0, 0, 0, 0, 0};
-        while (i < q_long.size()) {
-            const int l = list_of[q_long[i]];
-            const int64_t len = list_ptr[l + 1] - list_ptr[l];
-            size_t j = i;
-            while (j < q_long.size() && j - i < (size_t)erh::kDenseRowsGroup && list_of[q_long[j]] == l) ++j;
-            int ng = (int)(j - i);
-            if (c.doubles + len > ws_doubles && c.q1 > c.q0) {            // the chunk is full: it ends in front of this group
-                c.item1 = (int64_t)items.size();
-                chunks.push_back(c);
-                c = Chunk{(int)i, (int)i, (int64_t)items.size(), 0, 0};
-            }
-            ng = (int)std::min<int64_t>(ng, std::max<int64_t>(1, (ws_doubles - c.doubles) / len));   // (len <= N <= ws_doubles: at least one)
-            for (int g = 0; g < ng; ++g) { span_off[(size_t)q_long[i + g]] = c.doubles; c.doubles += len; }
-            for (int64_t i0 = 0; i0 < len; i0 += erh::kDenseRowsSeg)
-                items.push_back(erh::ErhRowsItem{list_ptr[l] + i0, (int32_t)std::min<int64_t>(erh::kDenseRowsSeg, len - i0), (int32_t)i0, (int32_t)i, ng});
-            i += (size_t)ng;
-            c.q1 = (int)i;
-        }
-        if (c.q1 > c.q0) { c.item1 = (int64_t)items.size(); chunks.push_back(c); }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    // work space first: a call that cannot have it enqueues nothing
-    int64_t need = 0;
-    for (const Chunk &c : chunks) need = std::max(need, c.doubles);
-    const size_t o_ptr = 0, o_span = o_ptr + ((size_t)n_lists + 1) * 8, o_rl = o_span + (size_t)B * 8, o_items = o_rl + SP.routed.size() * 8,
-                 o_rows = o_items + items.size() * sizeof(erh::ErhRowsItem), o_of = o_rows + (kept_rows ? 0 : (size_t)total * 4), o_short = o_of + (size_t)B * 4,
-                 o_long = o_short + q_short.size() * 4, tab_bytes = o_long + q_long.size() * 4;
-    const size_t q_bytes = (size_t)B * d * (q_dtype == ERH_F16 ? 2 : 4);
-    HostOut out(h, out_ids, out_scores, out_len, out_is_device, B, k);
-    out.b_ids = &h->rw_ids; out.b_sc = &h->rw_sc; out.b_len = &h->rw_len;
-    {
-        hipError_t e = hipSuccess;
-        if (need > 0) e = h->rw_s64.ensure((size_t)need * 8);
-        if (e == hipSuccess) e = h->rw_tab.ensure(tab_bytes);
-        if (e == hipSuccess) e = h->rw_q16.ensure((size_t)B * d * 2);
-        if (e == hipSuccess) e = h->rw_qn.ensure((size_t)B * 4);
-        if (e == hipSuccess && !q_is_device) e = h->rw_q.ensure(q_bytes);
-        if (e == hipSuccess && SP.n_routed) e = rows_classes_ensure(h->rwc, SP, N);
-        if (e == hipSuccess) e = out.ensure();
-        if (e != hipSuccess) { (void)hipGetLastError(); return h->fail(ERH_ERR_NOMEM, "erh_dense_topk_rows: work space", e); }
-    }
-    {
-        std::vector<char> tab(tab_bytes);
-        const int64_t zero = 0;
-        memcpy(tab.data() + o_ptr, n_lists > 0 ? (const void *)list_ptr : (const void *)&zero, ((size_t)n_lists + 1) * 8);
-        memcpy(tab.data() + o_span, span_off.data(), (size_t)B * 8);
-        if (!SP.routed.empty()) memcpy(tab.data() + o_rl, SP.routed.data(), SP.routed.size() * 8);
-        if (!items.empty()) memcpy(tab.data() + o_items, items.data(), items.size() * sizeof(erh::ErhRowsItem));
-        if (total > 0 && !kept_rows) memcpy(tab.data() + o_rows, list_rows, (size_t)total * 4);
-        memcpy(tab.data() + o_of, list_of, (size_t)B * 4);
-        if (!q_short.empty()) memcpy(tab.data() + o_short, q_short.data(), q_short.size() * 4);
-        if (!q_long.empty()) memcpy(tab.data() + o_long, q_long.data(), q_long.size() * 4);
-        HIPCHK(h, hipMemcpyAsync(h->rw_tab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
-        if (!q_is_device) HIPCHK(h, hipMemcpyAsync(h->rw_q.p, q, q_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipStreamSynchronize(st));               // (`tab` is pageable memory of this scope)
-    }
-    const char *T = h->rw_tab.as<char>();
-    const int64_t *d_ptr = reinterpret_cast<const int64_t *>(T + o_ptr), *d_span = reinterpret_cast<const int64_t *>(T + o_span);
-    const erh::ErhRowsItem *d_items = reinterpret_cast<const erh::ErhRowsItem *>(T + o_items);
-    const int32_t *d_rows = kept_rows ? kept_rows : reinterpret_cast<const int32_t *>(T + o_rows), *d_of = reinterpret_cast<const int32_t *>(T + o_of),
-                  *d_short = reinterpret_cast<const int32_t *>(T + o_short), *d_long = reinterpret_cast<const int32_t *>(T + o_long);
-    int32_t *d_ids = out.d_ids; double *d_sc = out.d_sc; int32_t *d_len = out.d_len;
-    const _Float16 *X = h->X.as<_Float16>();
-    const _Float16 *Q16 = h->rw_q16.as<_Float16>();
-    if (SP.n_routed) {
-        const erh::ErhRowsCell *cells = nullptr;
-        int n_cells = 0;
-        int rs = rows_classes_build(h, h->rwc, SP, d_rows, reinterpret_cast<const int64_t *>(T + o_rl), N, ERH_K_DENSE_SELECT, st, &cells, &n_cells);
-        if (rs < 0) return rs;
-        std::vector<int32_t> sub_ptr, src;
-        std::vector<int16_t> cls;
-        std::vector<uint64_t> sig((size_t)n_cells);
-        for (int c = 0; rs == 0 && c < n_cells; ++c) sig[(size_t)c] = cells[c].sig;
-        bool go = rs == 0 && rows_class_sets(sig.data(), n_cells, SP.n_routed, bit_of.data(), B, sub_ptr, src, cls);
-        if (go && scan_opt == 1) {                          // the rule again, now that the cells are known
-            int64_t n_small = 0;
-            for (int16_t c : cls) n_small += dense_rows_cell_is_small(h, cells[c].cnt, k) ? 1 : 0;
-            go = dense_rows_scan_pays(h, SP, (int64_t)src.size(), n_small);
-        }
-        if (!go) {                                          // nothing of the call has been written yet: all of it on today's shapes
-            const int32_t *kept = nullptr;
-            const int rk = rows_keep(h, h->rwc, d_rows, total, st, &kept);
-            if (rk != ERH_OK) return rk;
-            return dense_topk_rows_impl(h, q, q_dtype, q_is_device, normalize_q, B, k, n_lists, list_ptr, list_rows, list_of, out_ids, out_scores,
-                                        out_len, out_is_device, stream, kept);
-        }
-        {
-            CallClasses cc(h, h->rwc);
-            rs = cc.enter(cells, n_cells, N, false, st);
-            if (rs == ERH_OK) rs = dense_sets_run(h, q_is_device ? q : h->rw_q.p, q_dtype, normalize_q, B, k, sub_ptr, src, cls, ERH_DENSE_EXACT,
-                                                  d_ids, d_sc, d_len, st);
-            if (rs == ERH_OK) rs = dense_sets_check(h, st);   // (the flag words and the exhaustive rounds read the column: before it is restored)
-            h->forget_dense_call();                           // nothing of it is left for a later erh_dense_check; the diag words stay
-        }
-        if (rs != ERH_OK) return rs;
-        h->stats.dense_rows_scan_calls += 1;
-        h->stats.dense_rows_scan_subqueries += (int64_t)src.size();
-    }
-    h->stats.dense_rows_calls += 1;
-    if (!q_short.empty() || !chunks.empty()) {
-        ProfScope ps(h, st, ERH_K_DENSE_SELECT, 0, 0);
-        HIPCHK(h, erh::launch_prep_queries(q_is_device ? q : h->rw_q.p, q_dtype, normalize_q, B, B, d, h->rw_q16.as<_Float16>(), h->rw_qn.as<float>(),
-                                           nullptr, nullptr, st));
-    }
-    if (!q_short.empty()) {
-        int64_t n_rows = 0;
-        for (int32_t b : q_short) n_rows += len_of(b);
-        ProfScope ps(h, st, ERH_K_DENSE_SCAN, (double)n_rows * d * 2, 2.0 * (double)n_rows * d);
-        HIPCHK(h, erh::launch_dense_rows_short(X, N, d, h->pos_mul, Q16, d_rows, d_ptr, d_of, d_short, (int)q_short.size(), k, d_ids, d_sc, d_len, st));
-        h->stats.dense_rows_short += 1;
-    }
-    for (const Chunk &c : chunks) {
-        { ProfScope ps(h, st, ERH_K_DENSE_SCAN, 0, (double)c.doubles * d * 2.0);
-          HIPCHK(h, erh::launch_dense_rows_score(X, N, d, h->pos_mul, Q16, d_rows, d_items + c.item0, (int)(c.item1 - c.item0), d_long, d_span,
-                                                 h->rw_s64.as<double>(), st)); }
-        { ProfScope ps(h, st, ERH_K_DENSE_SELECT, (double)c.doubles * 8, 0);
-          HIPCHK(h, erh::launch_dense_rows_select(h->rw_s64.as<double>(), d_span, d_rows, d_ptr, d_of, d_long + c.q0, c.q1 - c.q0, k, d_ids, d_sc,
-                                                  d_len, st)); }
-        h->stats.dense_rows_long += 1;
-    }
-    return out.finish(st);
-}
-
-int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q, int B, int k,
-                        int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
-                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
-    if (!h) return ERH_ERR_INVALID;
-    return dense_topk_rows_impl(h, q, q_dtype, q_is_device, normalize_q, B, k, n_lists, list_ptr, list_rows, list_of, out_ids, out_scores, out_len,
-                                out_is_device, stream, nullptr);
-}
-
 int erh_bm25_topk(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
                   const int16_t *filter_dir,
                   int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
@@ -1500,252 +1170,11 @@ int erh_bm25_topk(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, 
     return rc == ERH_OK ? out.finish(st) : rc;
 }
 
-// Explicit row lists on the sparse route (bm25_rows.hip; launches: pipeline_bm25.hip, bm25_rows_dev).  Everything is checked on the host
-// before anything is enqueued; the call keeps to buffers of its own (bw_*) -- neither the query upload of erh_bm25_topk (qpack) nor the
-// staging rows of any other entry are touched, so a device-output call enqueued in front of it on the stream keeps its results -- and sets
-// no flag words.  Lists of at most kBm25RowsShortMax rows: one launch for all their queries; longer ones: score + select launches per chunk
-// of queries whose score spans fit the work space.
-//   The scan route (DESIGN K11): the call's long lists that the work rule sends there (options bm25_rows_scan, bm25_rows_scan_min_rows) become a
-// call-local class column over the slot's documents (rows_classes.hip) and their queries one set-filtered batch of the scan (bm25_sets_run)
-// on that column, installed for the call by a CallClasses guard.  That batch uses the scan's work space (qpack, part_*, bs_*): a routed call
-// is ordered with the handle's other scan calls like two erh_bm25_topk calls are.  The merge writes every row of the batch (an empty list
-// for the queries that are not on the route); the short and long shapes then overwrite theirs.
-// kept_rows: the call that the scan route handed back (too many cells, or the rule said no once the cells were known) -- the lists were
-// validated and uploaded by the first pass, which kept the row ids on the device (RowsClasses::keep): this pass neither checks nor uploads
-// them again, so a hand-back costs the classification and the small tables, not megabytes of row ids a second time.
-static bool bm25_rows_scan_pays(const erh_handle *h, const RowsScanPlan &P, int64_t N, int64_t n_sub, int64_t n_cells) {
-    // today's work: (query, listed row) pairs; the scan's: (sub-query, row) pairs, every cell counted as `floor` sub-queries more (what the
-    // scan route costs before its first sub-query, and with every further class a batch is spread over).  One constant (gain) relates the two.
-    double today = 0;
-    for (size_t l = 0; l < P.bit.size(); ++l)
-        if (P.bit[l] >= 0) today += (double)P.n_q[l] * (double)P.routed[2 * (size_t)P.bit[l] + 1];
-    const double scan = (double)N * ((double)n_sub + (double)h->opt_bm25_rows_scan_floor * (double)n_cells);
-    return today * (double)h->opt_bm25_rows_scan_gain > scan;
-}
-
-static int bm25_topk_rows_impl(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
-                               int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
-                               int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream, const int32_t *kept_rows) {
-    const bool allow_scan = kept_rows == nullptr;
-    const Bm25State &S = h->bm[h->cur];
-    if (S.variant < 0) return h->fail(ERH_ERR_STATE, "erh_bm25_topk_rows before erh_set_bm25_*");
-    if (!q_indptr || !out_ids || !out_scores || !out_len || !list_of || B <= 0) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: null pointer or non-positive B");
-    if (k < 1 || k > 1024) return h->fail(ERH_ERR_UNSUPPORTED, "erh_bm25_topk_rows: k outside [1, 1024]");
-    if (S.nnz >= ((int64_t)1 << 32)) return h->fail(ERH_ERR_UNSUPPORTED, "erh_bm25_topk_rows: more than 2^32 postings");
-    // the queries, as erh_bm25_topk takes them
-    if (q_indptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: q_indptr[0] must be 0");
-    for (int b = 0; b < B; ++b)
-        if (q_indptr[b + 1] < q_indptr[b]) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: q_indptr must be non-decreasing");
-    const int nt = q_indptr[B];
-    if (nt > 0 && !q_tok) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: null q_tok");
-    for (int i = 0; i < nt; ++i)
-        if (q_tok[i] < 0 || q_tok[i] >= S.V) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: query term id out of range");
-    // the lists: a monotone CSR from 0, every list strictly ascending inside [0, N)
-    if (n_lists < 0 || (n_lists > 0 && !list_ptr)) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: negative n_lists or null list_ptr");
-    const int64_t N = S.Nb;
-    int64_t total = 0;
-    if (n_lists > 0) {
-        if (list_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: list_ptr[0] != 0");
-        for (int l = 0; l < n_lists; ++l)
-            if (list_ptr[l + 1] < list_ptr[l]) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: list_ptr decreases");
-        total = list_ptr[n_lists];
-        if (total > 0 && !list_rows) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: null list_rows");
-        for (int l = 0; l < n_lists && allow_scan; ++l)
-            for (int64_t i = list_ptr[l]; i < list_ptr[l + 1]; ++i) {
-                const int32_t r = list_rows[i];
-                if (r < 0 || (int64_t)r >= N) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: row outside [0, N)");
-                if (i > list_ptr[l] && r <= list_rows[i - 1]) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: rows of a list must be strictly ascending");
-            }
-    }
-    for (int b = 0; b < B; ++b)
-        if (list_of[b] < -1 || list_of[b] >= n_lists) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_rows: list_of outside [-1, n_lists)");
-    auto len_of = [&](int b) -> int64_t { const int l = list_of[b]; return l < 0 ? 0 : list_ptr[l + 1] - list_ptr[l]; };
-    auto ntok_of = [&](int b) -> int64_t { return q_indptr[b + 1] - q_indptr[b]; };
-    // shapes by list length; the long queries in chunks whose spans (offsets relative to the chunk) fit the work space, one work item per
-    // (query, segment of kBm25RowsSeg rows)
-    Bm25RowsPlan P;
-    RowsScanPlan SP;                                                      // the scan route's lists first
-    const int scan_opt = allow_scan ? h->opt_bm25_rows_scan : 0;
-    rows_scan_candidates(scan_opt, h->opt_bm25_rows_scan_min_rows, n_lists, list_ptr, list_of, B, N, &SP);
-    if (SP.n_routed && scan_opt == 1 && !bm25_rows_scan_pays(h, SP, N, SP.n_queries, 1)) SP.clear();   // (a query is at least one sub-query, the lists at least one cell)
-    std::vector<int32_t> q_short, q_long, bit_of((size_t)B, -1);
-    for (int b = 0; b < B; ++b) {
-        if (list_of[b] >= 0 && SP.bit[(size_t)list_of[b]] >= 0) bit_of[(size_t)b] = SP.bit[(size_t)list_of[b]];
-        else (len_of(b) <= erh::kBm25RowsShortMax ? q_short : q_long).push_back(b);
-    }
-    for (int32_t b : q_short) P.short_searches += len_of(b) * ntok_of(b);
-    const int64_t ws_doubles = std::max<int64_t>((h->opt_bm25_rows_ws_mb << 20) / 8, N);
-    std::vector<int64_t> span_off((size_t)B, 0);
-    std::vector<erh::ErhBm25RowsItem> items;
-    {
-        Bm25RowsPlan::Chunk c{0, 0, 0, 0, 0, 0};
-        for (size_t i = 0; i < q_long.size(); ++i) {
-            const int32_t b = q_long[i];
-            const int64_t len = len_of(b);                                // (len <= N <= ws_doubles: a chunk holds at least one query)
-            if (c.doubles + len > ws_doubles && c.q1 > c.q0) {            // the chunk is full: it ends in front of this query
-                c.item1 = (int64_t)items.size();
-                P.chunks.push_back(c);
-                c = Bm25RowsPlan::Chunk{(int)i, (int)i, (int64_t)items.size(), 0, 0, 0};
-            }
-            span_off[(size_t)b] = c.doubles;
-            c.doubles += len;
-            c.searches += len * ntok_of(b);
-            for (int64_t i0 = 0; i0 < len; i0 += erh::kBm25RowsSeg)
-                items.push_back(erh::ErhBm25RowsItem{b, (int32_t)i0, (int32_t)std::min<int64_t>(erh::kBm25RowsSeg, len - i0)});
-            c.q1 = (int)i + 1;
-        }
-        if (c.q1 > c.q0) { c.item1 = (int64_t)items.size(); P.chunks.push_back(c); }
-    }
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    // work space first: a call that cannot have it enqueues nothing
-    int64_t need = 0;
-    for (const Bm25RowsPlan::Chunk &c : P.chunks) need = std::max(need, c.doubles);
-    const size_t o_ptr = 0, o_span = o_ptr + ((size_t)n_lists + 1) * 8, o_qptr = o_span + (size_t)B * 8, o_qtok = o_qptr + ((size_t)B + 1) * 4,
-                 o_rows = o_qtok + (size_t)nt * 4, o_of = o_rows + (kept_rows ? 0 : (size_t)total * 4), o_short = o_of + (size_t)B * 4,
-                 o_long = o_short + q_short.size() * 4, o_items = o_long + q_long.size() * 4,
-                 o_rl = (o_items + items.size() * sizeof(erh::ErhBm25RowsItem) + 7) / 8 * 8, tab_bytes = o_rl + SP.routed.size() * 8;
-    HostOut out(h, out_ids, out_scores, out_len, out_is_device, B, k);
-    out.b_ids = &h->bw_ids; out.b_sc = &h->bw_sc; out.b_len = &h->bw_len;
-    {
-        hipError_t e = hipSuccess;
-        if (need > 0) e = h->bw_s64.ensure((size_t)need * 8);
-        if (e == hipSuccess) e = h->bw_tab.ensure(tab_bytes);
-        if (e == hipSuccess && SP.n_routed) e = rows_classes_ensure(h->bwc, SP, N);
-        if (e == hipSuccess) e = out.ensure();
-        if (e != hipSuccess) { (void)hipGetLastError(); return h->fail(ERH_ERR_NOMEM, "erh_bm25_topk_rows: work space", e); }
-    }
-    {
-        std::vector<char> tab(tab_bytes);
-        const int64_t zero = 0;
-        memcpy(tab.data() + o_ptr, n_lists > 0 ? (const void *)list_ptr : (const void *)&zero, ((size_t)n_lists + 1) * 8);
-        memcpy(tab.data() + o_span, span_off.data(), (size_t)B * 8);
-        memcpy(tab.data() + o_qptr, q_indptr, ((size_t)B + 1) * 4);
-        if (nt > 0) memcpy(tab.data() + o_qtok, q_tok, (size_t)nt * 4);
-        if (total > 0 && !kept_rows) memcpy(tab.data() + o_rows, list_rows, (size_t)total * 4);
-        memcpy(tab.data() + o_of, list_of, (size_t)B * 4);
-        if (!q_short.empty()) memcpy(tab.data() + o_short, q_short.data(), q_short.size() * 4);
-        if (!q_long.empty()) memcpy(tab.data() + o_long, q_long.data(), q_long.size() * 4);
-        if (!items.empty()) memcpy(tab.data() + o_items, items.data(), items.size() * sizeof(erh::ErhBm25RowsItem));
-        if (!SP.routed.empty()) memcpy(tab.data() + o_rl, SP.routed.data(), SP.routed.size() * 8);
-        HIPCHK(h, hipMemcpyAsync(h->bw_tab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipStreamSynchronize(st));               // (`tab` is pageable memory of this scope)
-    }
-    const char *T = h->bw_tab.as<char>();
-    P.d_ptr = reinterpret_cast<const int64_t *>(T + o_ptr); P.d_span = reinterpret_cast<const int64_t *>(T + o_span);
-    P.d_qptr = reinterpret_cast<const int32_t *>(T + o_qptr); P.d_qtok = reinterpret_cast<const int32_t *>(T + o_qtok);
-    P.d_rows = kept_rows ? kept_rows : reinterpret_cast<const int32_t *>(T + o_rows); P.d_of = reinterpret_cast<const int32_t *>(T + o_of);
-    P.d_short = reinterpret_cast<const int32_t *>(T + o_short); P.d_long = reinterpret_cast<const int32_t *>(T + o_long);
-    P.d_items = reinterpret_cast<const erh::ErhBm25RowsItem *>(T + o_items);
-    P.n_short = (int)q_short.size();
-    if (SP.n_routed) {
-        const erh::ErhRowsCell *cells = nullptr;
-        int n_cells = 0;
-        int rs = rows_classes_build(h, h->bwc, SP, P.d_rows, reinterpret_cast<const int64_t *>(T + o_rl), N, ERH_K_BM25_MERGE, st, &cells, &n_cells);
-        if (rs < 0) return rs;
-        std::vector<int32_t> sub_ptr, src;
-        std::vector<int16_t> cls;
-        std::vector<uint64_t> sig((size_t)n_cells);
-        for (int c = 0; rs == 0 && c < n_cells; ++c) sig[(size_t)c] = cells[c].sig;
-        bool go = rs == 0 && rows_class_sets(sig.data(), n_cells, SP.n_routed, bit_of.data(), B, sub_ptr, src, cls);
-        go = go && bm25_sets_tokens_fit(q_indptr, src);
-        if (go && scan_opt == 1 && !bm25_rows_scan_pays(h, SP, N, (int64_t)src.size(), n_cells)) go = false;   // the rule again, the cells known
-        if (!go) {                                          // nothing of the call has been written yet: all of it on today's shapes
-            const int32_t *kept = nullptr;
-            const int rk = rows_keep(h, h->bwc, P.d_rows, total, st, &kept);
-            if (rk != ERH_OK) return rk;
-            return bm25_topk_rows_impl(h, q_indptr, q_tok, B, k, n_lists, list_ptr, list_rows, list_of, out_ids, out_scores, out_len, out_is_device,
-                                       stream, kept);
-        }
-        {
-            CallClasses cc(h, h->bwc);
-            rs = cc.enter(cells, n_cells, N, h->opt_bm25_dir_range != 0, st);
-            if (rs == ERH_OK) rs = bm25_sets_run(h, "erh_bm25_topk_rows", q_indptr, q_tok, B, k, sub_ptr, src, cls, out.d_ids, out.d_sc, out.d_len, st);
-        }
-        if (rs != ERH_OK) return rs;
-        h->stats.bm25_rows_scan_calls += 1;
-        h->stats.bm25_rows_scan_subqueries += (int64_t)src.size();
-    }
-    h->stats.bm25_rows_calls += 1;
-    const int rc = bm25_rows_dev(h, P, k, out.d_ids, out.d_sc, out.d_len, st);
-    return rc == ERH_OK ? out.finish(st) : rc;
-}
-
-int erh_bm25_topk_rows(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
-                       int n_lists, const int64_t *list_ptr, const int32_t *list_rows, const int32_t *list_of,
-                       int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
-    if (!h) return ERH_ERR_INVALID;
-    return bm25_topk_rows_impl(h, q_indptr, q_tok, B, k, n_lists, list_ptr, list_rows, list_of, out_ids, out_scores, out_len, out_is_device,
-                               stream, nullptr);
-}
-
 // Set filters on the sparse route, the twin of erh_dense_topk_sets: every (query, allowed class) pair is a sub-query of ordinary class-column
 // batches through upload_bm25_queries + bm25_topk_dev (chunks of kBm25SetsChunk sub-queries, one behind the other on the stream), whose
 // lists go to bs_ids / bs_sc / bs_len; then ONE merge launch (bm25_sets.hip) builds each query's list from its sub-lists -- after the last
 // chunk, since a query's sub-queries may straddle a chunk boundary.  An unfiltered query ({-1}) is one sub-query without a class, an empty
 // set none, a class no document carries none.  Everything is checked on the host before anything is enqueued; no flag words are set.
-// (kBm25SetsChunk: declared with the scan route of the rows entries, above)
-
-// The sub-query batch of a set-filtered BM25 call behind validation: chunk after chunk through upload_bm25_queries + bm25_topk_dev into
-// bs_ids / bs_sc / bs_len, then the merge into d_ids / d_sc / d_len [B x k].  Shared by erh_bm25_topk_sets and the scan route of
-// erh_bm25_topk_rows, which runs it on a call-local class column (CallClasses).  The caller has checked that a chunk's tokens fit 32 bits
-// (bm25_sets_tokens_fit) and counts its own stats.
-static bool bm25_sets_tokens_fit(const int32_t *q_indptr, const std::vector<int32_t> &src) {
-    const int n_sub = (int)src.size();
-    for (int c0 = 0; c0 < n_sub; c0 += kBm25SetsChunk) {             // a chunk's query CSR has 32-bit offsets
-        int64_t toks = 0;
-        for (int i = c0; i < std::min(n_sub, c0 + kBm25SetsChunk); ++i) toks += q_indptr[src[i] + 1] - q_indptr[src[i]];
-        if (toks > 2147483647LL) return false;
-    }
-    return true;
-}
-
-static int bm25_sets_run(erh_handle *h, const char *who, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
-                         const std::vector<int32_t> &sub_ptr, const std::vector<int32_t> &src, const std::vector<int16_t> &cls,
-                         int32_t *d_ids, double *d_sc, int32_t *d_len, hipStream_t st) {
-    const Bm25State &S = h->bm[h->cur];
-    const int n_sub = (int)src.size();
-    // buffers first: a call that cannot have them enqueues nothing
-    {
-        hipError_t e = h->bs_tab.ensure(((size_t)B + 1) * 4);
-        if (e == hipSuccess && n_sub > 0) e = h->bs_ids.ensure((size_t)n_sub * k * 4);
-        if (e == hipSuccess && n_sub > 0) e = h->bs_sc.ensure((size_t)n_sub * k * 8);
-        if (e == hipSuccess && n_sub > 0) e = h->bs_len.ensure((size_t)n_sub * 4);
-        if (e != hipSuccess) { (void)hipGetLastError(); return h->fail(ERH_ERR_NOMEM, (std::string(who) + ": work space").c_str(), e); }
-    }
-    HIPCHK(h, hipMemcpyAsync(h->bs_tab.p, sub_ptr.data(), ((size_t)B + 1) * 4, hipMemcpyHostToDevice, st));
-    // (`sub_ptr` is pageable memory of the caller's scope -- and whatever was enqueued in front of this call has now read the query staging
-    // (qpack_host) that the first chunk is about to overwrite)
-    HIPCHK(h, hipStreamSynchronize(st));
-    std::vector<int32_t> c_ptr, c_tok;
-    for (int c0 = 0; c0 < n_sub; c0 += kBm25SetsChunk) {
-        const int nb = std::min(kBm25SetsChunk, n_sub - c0);
-        c_ptr.assign((size_t)nb + 1, 0);
-        c_tok.clear();
-        bool filtered = false;
-        for (int i = 0; i < nb; ++i) {
-            const int b = src[(size_t)c0 + i];
-            if (q_indptr[b + 1] > q_indptr[b]) c_tok.insert(c_tok.end(), q_tok + q_indptr[b], q_tok + q_indptr[b + 1]);
-            c_ptr[(size_t)i + 1] = (int32_t)c_tok.size();
-            filtered = filtered || cls[(size_t)c0 + i] >= 0;
-        }
-        // the upload below rewrites the host staging of the query CSR: the previous chunk's copy must have read it
-        if (c0 > 0) HIPCHK(h, hipStreamSynchronize(st));
-        double bytes = 0;
-        int max_qlen = 0;
-        const int16_t *filt = nullptr;
-        int rc = upload_bm25_queries(h, c_ptr.data(), c_tok.data(), nb, st, S.host_indptr, &bytes, &max_qlen,
-                                     filtered ? cls.data() + c0 : nullptr, &filt);
-        if (rc != ERH_OK) return rc;
-        rc = bm25_topk_dev(h, h->qptr, h->qtok, nb, k, filt, h->bs_ids.as<int32_t>() + (size_t)c0 * k, h->bs_sc.as<double>() + (size_t)c0 * k,
-                           h->bs_len.as<int32_t>() + c0, bytes, max_qlen, st);
-        if (rc != ERH_OK) return rc;
-    }
-    { ProfScope ps(h, st, ERH_K_BM25_MERGE, (double)n_sub * k * 12, 0);
-      HIPCHK(h, erh::launch_bm25_set_merge(h->bs_ids.as<int32_t>(), h->bs_sc.as<double>(), h->bs_len.as<int32_t>(), h->bs_tab.as<int32_t>(), B, k,
-                                           d_ids, d_sc, d_len, st)); }
-    return ERH_OK;
-}
 
 int erh_bm25_topk_sets(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
                        const int32_t *set_ptr, const int16_t *set_cls,
@@ -1756,14 +1185,8 @@ int erh_bm25_topk_sets(erh_handle *h, const int32_t *q_indptr, const int32_t *q_
     if (!q_indptr || !set_ptr || !out_ids || !out_scores || !out_len || B <= 0)
         return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: null pointer or non-positive B");
     if (k < 1 || k > 1024) return h->fail(ERH_ERR_UNSUPPORTED, "erh_bm25_topk_sets: k outside [1, 1024]");
-    // the queries, as erh_bm25_topk takes them
-    if (q_indptr[0] != 0) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: q_indptr[0] must be 0");
-    for (int b = 0; b < B; ++b)
-        if (q_indptr[b + 1] < q_indptr[b]) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: q_indptr must be non-decreasing");
-    const int nt = q_indptr[B];
-    if (nt > 0 && !q_tok) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: null q_tok");
-    for (int i = 0; i < nt; ++i)
-        if (q_tok[i] < 0 || q_tok[i] >= S.V) return h->fail(ERH_ERR_INVALID, "erh_bm25_topk_sets: query term id out of range");
+    const int rc_q = check_bm25_queries(h, "erh_bm25_topk_sets", q_indptr, q_tok, B, S.V);
+    if (rc_q != ERH_OK) return rc_q;
     // the sets, as erh_dense_topk_sets takes them, and the sub-query batch they stand for
     const int rc_sets = check_class_sets(h, "erh_bm25_topk_sets", set_ptr, set_cls, B, S.Nb);
     if (rc_sets != ERH_OK) return rc_sets;
@@ -1786,19 +1209,6 @@ int erh_bm25_topk_sets(erh_handle *h, const int32_t *q_indptr, const int32_t *q_
     h->stats.bm25_sets_subqueries += (int64_t)src.size();
     h->stats.bm25_sets_merge_launches += 1;
     return out.finish(st);
-}
-
-int erh_debug_rows_class_sets(int n_cells, const uint64_t *cell_sig, int n_routed, int B, const int32_t *bit_of, int32_t *sub_ptr,
-                              int16_t *sub_cls, int sub_cap) {
-    if (n_cells < 0 || (n_cells > 0 && !cell_sig) || B < 0 || (B > 0 && !bit_of) || !sub_ptr || sub_cap < 0 || (sub_cap > 0 && !sub_cls))
-        return ERH_ERR_INVALID;
-    std::vector<int32_t> ptr, src;
-    std::vector<int16_t> cls;
-    if (!rows_class_sets(cell_sig, n_cells, n_routed, bit_of, B, ptr, src, cls)) return ERH_ERR_UNSUPPORTED;
-    if ((int64_t)cls.size() > (int64_t)sub_cap) return ERH_ERR_NOMEM;
-    memcpy(sub_ptr, ptr.data(), ((size_t)B + 1) * 4);
-    if (!cls.empty()) memcpy(sub_cls, cls.data(), cls.size() * 2);
-    return ERH_OK;
 }
 
 int erh_bm25_scores(erh_handle *h, const int32_t *q_tok, int n_tok, double *out_scores) {

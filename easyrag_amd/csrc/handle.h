@@ -215,27 +215,30 @@ struct erh_handle {
     } sets;
     DevBuf s_tab, s_q, s_ids, s_sc, s_len;   // s_tab: sub_ptr int32[B+1] | source row int32[n_sub] | class int16[n_sub], one upload
     // erh_dense_topk_rows (dense_rows.hip): buffers of its own, so that a rows call between a device-output dense call and its erh_dense_check
-    // leaves that call's query block, flag words and lists alone.  rw_tab: ONE upload per call -- list_ptr | span offsets | work items | rows |
-    // list_of | short-shape queries | long-shape queries; rw_s64: the long shape's score spans (opt_rows_ws_mb, at least one list of N rows)
+    // leaves that call's query block, flag words and lists alone.  rw_tab: the call's small tables, ONE upload per call, laid out by a
+    // TableBuilder in the entry (the row ids are not in it: rwc.rows); rw_s64: the long shape's score spans (opt_rows_ws_mb, at least one
+    // list of N rows)
     DevBuf rw_tab, rw_q, rw_q16, rw_qn, rw_s64, rw_ids, rw_sc, rw_len;
     int64_t opt_rows_ws_mb = 256;
     // erh_bm25_topk_rows (bm25_rows.hip): again buffers of its own, so that a rows call enqueued behind a device-output erh_bm25_topk /
-    // erh_dense_topk / erh_dense_topk_rows on the same stream leaves that call's query upload, lists and staging alone.  bw_tab: ONE upload
-    // per call -- list_ptr | span offsets | q_indptr | q_tok | rows | list_of | short-shape queries | long-shape queries | work items;
+    // erh_dense_topk / erh_dense_topk_rows on the same stream leaves that call's query upload, lists and staging alone.  bw_tab: the call's
+    // small tables with its query CSR, ONE upload per call, laid out by a TableBuilder in the entry (the row ids are not in it: bwc.rows);
     // bw_s64: the long shape's score spans (opt_bm25_rows_ws_mb, at least one list of N rows)
     DevBuf bw_tab, bw_s64, bw_ids, bw_sc, bw_len;
     int64_t opt_bm25_rows_ws_mb = 256;
     // erh_bm25_topk_sets (bm25_sets.hip): the sub-queries' lists [n_sub x k] that its class-column scans write and its merge reads, and
     // bs_tab: sub_ptr int32[B + 1], one upload per call.  The scans themselves use what erh_bm25_topk uses (qpack, part_*).
     DevBuf bs_tab, bs_ids, bs_sc, bs_len;
-    // Scan route of the rows entries (rows_classes.hip, DESIGN K11): the long lists of a call numbered as a CALL-LOCAL class column that the
-    // sets pipelines run on in place of the handle's own.  Buffers of the rows routes, one set per route (the two corpora may differ in size);
-    // the next routed call of the route reuses them in stream order.  sig: uint64[N] membership words; cls: int16[N] the column; pos: its
-    // copy by stored position (dense, built by the pipeline on demand); table: header | cells | open-addressing table; rng: the cells' row
-    // ranges as bm25_dir_range reads them.
+    // The rows entries (rows_entries.hip), one set of buffers per route (the two corpora may differ in size); the next call of the route
+    // reuses them in stream order.  rows: the call's row ids, every call's, copied straight from the caller's array -- read by the
+    // row-by-row shapes and by the classification alike, whichever of them the call ends up on.  The rest is the scan route's (rows_classes.hip,
+    // DESIGN K11), which numbers the long lists of a call as a CALL-LOCAL class column that the sets pipelines run on in place of the
+    // handle's own.  sig: uint64[N] membership words; cls: int16[N] the column; pos: its copy by stored position (dense, built by the
+    // pipeline on demand); table: routed-list pairs | header | cells | open-addressing table; rng: the cells' row ranges as bm25_dir_range
+    // reads them.
     struct RowsClasses {
+        DevBuf rows;
         DevBuf sig, cls, pos, table, rng;
-        DevBuf keep;                                                   // the call's uploaded row ids, kept across a hand-back to the row-by-row shapes
         std::vector<char> cells_host;                                  // header + cells as read back
         std::vector<int32_t> rng_host;
     } rwc, bwc;
@@ -434,6 +437,28 @@ inline void drain_events(erh_handle *h) {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// The small tables of a call as ONE upload: every section is appended with its element type and aligned to it, and read back on the device
+// through the handle that add() returned -- the layout is written once.  upload() enqueues the copy from pageable memory of this object:
+// synchronise the stream before the builder goes out of scope.
+struct TableBuilder {
+    template <typename T> struct Section { size_t off; };
+    std::vector<char> host;
+    const char *dev = nullptr;
+    template <typename T> Section<T> add(const T *p, size_t n) {
+        const size_t off = (host.size() + alignof(T) - 1) / alignof(T) * alignof(T);
+        host.resize(off + n * sizeof(T));
+        if (n) memcpy(host.data() + off, p, n * sizeof(T));
+        return {off};
+    }
+    template <typename T> Section<T> add(const std::vector<T> &v) { return add(v.data(), v.size()); }
+    hipError_t upload(DevBuf &buf, hipStream_t st) {
+        const hipError_t e = buf.ensure(host.size());
+        dev = buf.as<char>();
+        return e != hipSuccess ? e : hipMemcpyAsync(buf.p, host.data(), host.size(), hipMemcpyHostToDevice, st);
+    }
+    template <typename T> const T *at(Section<T> s) const { return reinterpret_cast<const T *>(dev + s.off); }
+};
+
 // Multiplier pair of the row placement (see erh_handle::pos_mul): inv ~ n / golden ratio, coprime with n; mul = inv^-1 mod n.
 inline void choose_placement(int64_t n, int64_t *mul, int64_t *inv) {
     auto gcd = [](int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; };
@@ -457,6 +482,45 @@ int dense_topk_routed(erh_handle *h, const void *q_dev, int q_dtype, int normali
                       const int16_t *filter_dev, int mode, int32_t *d_ids, double *d_sc, int32_t *d_len, hipStream_t st);
 int dense_check_flags(erh_handle *h, hipStream_t st);
 int dense_sets_check(erh_handle *h, hipStream_t st);   // erh_dense_check after erh_dense_topk_sets (api.hip)
+// What the rows entries (rows_entries.hip) share with the dense and sparse entries of api.hip: the argument checks, and the sub-query batch
+// of a set-filtered call behind its validation, which their scan route runs on a call-local class column.
+int check_dense_args(erh_handle *h, const char *who, const void *q, bool outs, int B, int k, int q_dtype, int mode);
+int check_bm25_queries(erh_handle *h, const char *who, const int32_t *q_indptr, const int32_t *q_tok, int B, int64_t V);
+int dense_sets_run(erh_handle *h, const void *qd, int q_dtype, int normalize_q, int B, int k, const std::vector<int32_t> &sub_ptr,
+                   const std::vector<int32_t> &src, const std::vector<int16_t> &cls, int mode, int32_t *d_ids, double *d_sc, int32_t *d_len,
+                   hipStream_t st);
+bool bm25_sets_tokens_fit(const int32_t *q_indptr, const std::vector<int32_t> &src);
+int bm25_sets_run(erh_handle *h, const char *who, const int32_t *q_indptr, const int32_t *q_tok, int B, int k,
+                  const std::vector<int32_t> &sub_ptr, const std::vector<int32_t> &src, const std::vector<int16_t> &cls,
+                  int32_t *d_ids, double *d_sc, int32_t *d_len, hipStream_t st);
+// Where a call's kernels write its top-k lists: the caller's rows when they are on the device, else staging buffers of the handle
+// (o_* unless the call names its own) that finish() copies to the caller's host rows.
+struct HostOut {
+    erh_handle *h;
+    int32_t *out_ids; double *out_sc; int32_t *out_len;             // the caller's rows
+    bool host;
+    int B, k;
+    DevBuf *b_ids = &h->o_ids, *b_sc = &h->o_sc, *b_len = &h->o_len;   // the staging buffers (erh_dense_topk_rows points them at its own)
+    int32_t *d_ids; double *d_sc; int32_t *d_len;                   // where the kernels write
+    HostOut(erh_handle *h_, int32_t *ids, double *sc, int32_t *len, int out_is_device, int B_, int k_)
+        : h(h_), out_ids(ids), out_sc(sc), out_len(len), host(!out_is_device), B(B_), k(k_), d_ids(ids), d_sc(sc), d_len(len) {}
+    hipError_t ensure() {                                           // before the first kernel that writes the lists
+        if (!host) return hipSuccess;
+        hipError_t e = b_ids->ensure((size_t)B * k * 4);
+        if (e == hipSuccess) e = b_sc->ensure((size_t)B * k * 8);
+        if (e == hipSuccess) e = b_len->ensure((size_t)B * 4);
+        d_ids = b_ids->as<int32_t>(); d_sc = b_sc->as<double>(); d_len = b_len->as<int32_t>();
+        return e;
+    }
+    int finish(hipStream_t st) {                                    // the call's last step: lists to the host (synchronises), or nothing
+        if (!host) return ERH_OK;
+        HIPCHK(h, hipMemcpyAsync(out_ids, d_ids, (size_t)B * k * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(out_sc, d_sc, (size_t)B * k * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(out_len, d_len, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        return ERH_OK;
+    }
+};
 int bm25_topk_dev(erh_handle *h, const int32_t *qptr_dev, const int32_t *qtok_dev, int B, int k,
                   const int16_t *filter_dev, int32_t *d_ids, double *d_sc, int32_t *d_len, double postings_bytes,
                   int max_qlen, hipStream_t st);

@@ -267,7 +267,9 @@ int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_devi
  *     does not take the scan route (it would overwrite that call's work space): it runs on the row-by-row shapes, as before.
  * The same fall-back, for the whole call and without error, when it names more than 64 routable lists or they cut the rows into more than
  * 32766 cells (the classification stops at the first cell too many: it costs a few passes over N words, never a walk of its table per row;
- * the row ids stay on the device for the row-by-row pass and are not validated or uploaded again).  A routed call counts once in dense_rows_calls and dense_rows_scan_calls, not in dense_rows_long_launches and not in
+ * the call then carries on in the same pass -- its lists were validated once and its row ids uploaded once, whichever shapes answer it).
+ * The entry has read list_rows (and every other host array of the call) when it returns, device outputs on a stream included.  A routed
+ * call counts once in dense_rows_calls and dense_rows_scan_calls, not in dense_rows_long_launches and not in
  * dense_calls; its scans move the dense_scan_*_launches / dense_sample_passes counters and dense_candidates_last_call /
  * dense_rescored_rows_last_call like any scan-route call. */
 int erh_dense_topk_rows(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q, int B, int k,

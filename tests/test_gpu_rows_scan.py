@@ -668,6 +668,236 @@ def test_bm25_device_outputs_on_a_stream(eng):
     _same_bytes(host, out)
 
 
+# ---- one pass per call: the hand-back on the rule's second answer, the caller's row array, the shared argument checks ----------------------
+SN, SD = 8192, 128                         # the small corpus of the three groups below: 8192 rows / documents, dense d = 128
+_SMALL = {}
+
+
+def _small_dense():
+    if "dense" not in _SMALL:
+        rng = np.random.default_rng(3001)
+        x = _unit16(SN, SD, rng)
+        base = to_f16_unit(x[rng.integers(0, SN, NB)].astype(np.float32) + 0.7 * rng.standard_normal((NB, SD)).astype(np.float32) / np.sqrt(SD))
+        _SMALL["dense"] = (x, base, np.stack([dense_exact_scores(x, base[j]) for j in range(NB)]))
+    return _SMALL["dense"]
+
+
+def _small_bm25():
+    if "bm25" not in _SMALL:
+        flat, lens = synth.token_corpus(SN, VOCAB, seed=5, mean_len=20)
+        docs = [list(map(int, d)) for d in synth.split_docs(flat, lens)]
+        ora = _oracle_for(BM25S, docs)
+        idx = build_bm25_index(docs, BM25S)
+        queries = [list(map(int, q)) for q in synth.token_queries(flat, lens, VOCAB, NQ, seed=12)]
+        _SMALL["bm25"] = dict(idx=idx, queries=queries, S=np.stack([_scores(ora, q, SN) for q in queries]))
+    return _SMALL["bm25"]
+
+
+def _mixed_lists(a, b, rng):
+    """Two overlapping lists `a`, `b` with 4 queries each, one short list (300 rows), one long list below the raised minimum (2200 rows
+    against 2500), and a query without a list."""
+    lists = [np.asarray(a, np.int64), np.asarray(b, np.int64), _pick(rng, SN, 300), _pick(rng, SN, 2200)]
+    return lists, np.array([0, 1, 2, 0, 1, 3, 0, 1, -1, 0, 1, 2], np.int32)
+
+
+def _second_answer_no(eng, route, names, call, opts):
+    """The three assertions of the hand-back tests: with `*_rows_scan` = 1 and `opts` the call is answered on the row-by-row shapes although
+    its lists were candidates, with the bytes of the route-off call; with `*_rows_scan` = 2 the same call routes."""
+    saved = {o: eng.get_option(o) for o in opts}
+    try:
+        eng.set_option(route + "_rows_scan_min_rows", 2500)
+        for o, v in opts.items():
+            eng.set_option(o, v)
+        eng.set_option(route + "_rows_scan", 1)
+        st = _stats(eng, names)
+        got = call()
+        mv, st = _moved(eng, names, st)
+        assert (mv[route + "_rows_calls"], mv[route + "_rows_scan_calls"], mv[route + "_rows_scan_subqueries"]) == (1, 0, 0), mv
+        assert mv[route + "_rows_long_launches"] >= 1 and mv[route + "_rows_short_launches"] == 1, mv
+        eng.set_option(route + "_rows_scan", 0)
+        want = call()
+        mv, st = _moved(eng, names, st)
+        assert mv[route + "_rows_scan_calls"] == 0 and mv[route + "_rows_long_launches"] >= 1, mv
+        _same_bytes(got, want)
+        eng.set_option(route + "_rows_scan", 2)
+        routed = call()
+        mv, st = _moved(eng, names, st)
+        assert (mv[route + "_rows_calls"], mv[route + "_rows_scan_calls"]) == (1, 1), mv      # the lists were candidates
+        _same_bytes(got, routed)
+        return got
+    finally:
+        for o, v in saved.items():
+            eng.set_option(o, v)
+        eng.set_option(route + "_rows_scan_min_rows", 2049)
+        eng.set_option(route + "_rows_scan", 2)
+
+
+def test_dense_hand_back_on_the_second_answer_in_a_mixed_call(eng):
+    """The rule says yes before the cells are known and no after; the call carries on, in the same pass, on the row-by-row shapes.
+    N = 8192, k = 10, lists [0, 3000) and [2995, 6000) with 4 queries each, dense_rows_scan_small_cell = 1000, gain 700 and ridge 160
+    (the defaults).  The row-by-row work (dense_rows_scan_pays): one group of <= 8 queries per list, (3000 + 3005) x 700 = 4 203 500.
+    First answer: 8 sub-queries, none known to be small -> 8192 x max(8, 160) = 1 310 720 < 4 203 500: yes.  The cells are [0, 2995),
+    [2995, 3000) and [3000, 6000); the seed prefix is min(dense_n0, N) = N rows, so a cell is small when it has fewer than k = 10 rows
+    (dense_rows_cell_is_small): the 5-row cell is.  Second answer: 16 sub-queries, 8 of them on the small cell ->
+    8192 x (8 + 8 x 1000) = 65 601 536 >= 4 203 500: no.  (At the default small_cell = 13 the call would route: 8 + 104 < 160.)"""
+    x, base, S = _small_dense()
+    eng.set_dense(x)
+    eng.set_doc_meta(SN, None, None)
+    assert eng.get_option("dense_rows_scan_gain") == 700 and eng.get_option("dense_route_ridge") == 160 and eng.get_option("dense_n0") >= SN
+    lists, lo = _mixed_lists(np.arange(0, 3000), np.arange(2995, 6000), np.random.default_rng(43))
+    q = base[np.arange(len(lo)) % NB]
+    got = _second_answer_no(eng, "dense", DSTATS, lambda: eng.dense_topk_rows(q, 10, lists, list_of=lo), {"dense_rows_scan_small_cell": 1000})
+    _dense_check(got, S, lists, lo, 10, "hand-back")
+
+
+def test_bm25_hand_back_on_the_second_answer_in_a_mixed_call(eng):
+    """The sparse twin.  N = 8192, lists [0, 3000) and [1500, 4500) with 4 queries each, bm25_rows_scan_floor = 20, bm25_rows_scan_gain = 16.
+    The row-by-row work (bm25_rows_scan_pays): 8 queries x 3000 rows x 16 = 384 000.  First answer: 8 sub-queries and one cell at the least
+    -> 8192 x (8 + 20 x 1) = 229 376 < 384 000: yes.  The cells are [0, 1500), [1500, 3000) and [3000, 4500), two per list: 16
+    sub-queries.  Second answer: 8192 x (16 + 20 x 3) = 622 592 >= 384 000: no."""
+    c = _small_bm25()
+    idx, S = c["idx"], c["S"]
+    eng.set_bm25(idx)
+    eng.set_doc_meta(SN, None, None)
+    lists, lo = _mixed_lists(np.arange(0, 3000), np.arange(1500, 4500), np.random.default_rng(47))
+    csr = _csr(idx, [c["queries"][b % NQ] for b in range(len(lo))])
+    got = _second_answer_no(eng, "bm25", BSTATS, lambda: eng.bm25_topk_rows(*csr, 50, lists, list_of=lo),
+                            {"bm25_rows_scan_floor": 20, "bm25_rows_scan_gain": 16})
+    _bm25_check(got, lambda b: S[b % NQ], lists, lo, 50, "hand-back")
+
+
+@pytest.mark.parametrize("route", ["dense", "bm25"])
+def test_the_callers_row_array_is_free_on_return(eng, route):
+    """Device outputs on a stream of the caller's: the entry has read list_rows when it returns, whether the call is routed or not -- the
+    array is overwritten with zeros right behind the call, and the lists that arrive after the synchronisation are those of the rows."""
+    import torch
+    rng = np.random.default_rng(53)
+    lists = [_pick(rng, SN, 5000), _pick(rng, SN, 2049), _pick(rng, SN, 400)]
+    if route == "dense":
+        x, base, _ = _small_dense()
+        eng.set_dense(x)
+        names, B = DSTATS, 11
+        q = base[np.arange(B) % NB]
+        host_call = lambda lo: eng.dense_topk_rows(q, 100, lists, list_of=lo)
+        dev_call = lambda ptr, rows, lo, s: eng.dense_topk_rows_csr(q, 100, ptr, rows, lo, device_out=True, stream=s)
+    else:
+        c = _small_bm25()
+        eng.set_bm25(c["idx"])
+        names, B = BSTATS, NQ
+        csr = _csr(c["idx"], c["queries"])
+        host_call = lambda lo: eng.bm25_topk_rows(*csr, 100, lists, list_of=lo)
+        dev_call = lambda ptr, rows, lo, s: eng.bm25_topk_rows_csr(*csr, 100, ptr, rows, lo, device_out=True, stream=s)
+    eng.set_doc_meta(SN, None, None)
+    lo = (np.arange(B) % 3).astype(np.int32)
+    want = host_call(lo)
+    s2 = torch.cuda.Stream(device=torch.device("cuda", 0))
+    torch.cuda.synchronize()
+    try:
+        for scan, scan_calls in ((2, 1), (0, 0)):
+            eng.set_option(route + "_rows_scan", scan)
+            ptr, rows, _ = eng.lists_to_csr(lists, lo, B)
+            st = _stats(eng, names)
+            out = dev_call(ptr, rows, lo, s2)
+            rows[:] = 0                                                      # the caller's array, the one the entry was given
+            eng.sync(s2)
+            mv, st = _moved(eng, names, st)
+            assert (mv[route + "_rows_calls"], mv[route + "_rows_scan_calls"], mv[route + "_rows_short_launches"]) == (1, scan_calls, 1), (scan, mv)
+            assert (mv[route + "_rows_long_launches"] == 0) == (scan == 2), (scan, mv)
+            _same_bytes(want, out)
+    finally:
+        eng.set_option(route + "_rows_scan", 2)
+
+
+def _refused(eng, names, call, entry, message):
+    """`call(ids, sc, ln)` is refused as an invalid argument with `entry`'s own name in front of `message` in the handle's error text (behind
+    the status words every error text begins with); outputs untouched, no counter moved."""
+    ids, sc, ln = np.full((NQ, 3), 77, np.int32), np.full((NQ, 3), 7.5, np.float64), np.full(NQ, 77, np.int32)
+    st = _stats(eng, names)
+    rc = call(ids, sc, ln)
+    text = eng._lib.erh_last_error(eng._h).decode()
+    assert rc == _lib.ERH_ERR_INVALID, (entry, message, rc)
+    assert text == "invalid argument: " + entry + ": " + message, (entry, message, text)
+    assert np.all(ids == 77) and np.all(sc == 7.5) and np.all(ln == 77), (entry, message)
+    assert _moved(eng, names, st)[0] == dict.fromkeys(names, 0), (entry, message)
+
+
+def _malformed_lists():
+    """(message, list_ptr, list_rows, list_of) of the five malformed list arguments: two lists of 3000 rows, NQ queries."""
+    ptr = np.array([0, 3000, 6000], np.int64)
+    rows = np.concatenate([np.arange(0, 3000), np.arange(2000, 5000)]).astype(np.int32)
+    lo = (np.arange(NQ) % 2).astype(np.int32)
+    at_n, twice, past = rows.copy(), rows.copy(), lo.copy()
+    at_n[2999] = SN
+    twice[4000] = twice[3999]
+    past[NQ - 1] = 2
+    return [("list_ptr[0] != 0", np.array([1, 3000, 6000], np.int64), rows, lo),
+            ("list_ptr decreases", np.array([0, 3000, 2999], np.int64), rows, lo),
+            ("row outside [0, N)", ptr, at_n, lo),
+            ("rows of a list must be strictly ascending", ptr, twice, lo),
+            ("list_of outside [-1, n_lists)", ptr, rows, past)], (ptr, rows, lo)
+
+
+def test_dense_error_strings_name_the_entry(eng):
+    x, base, S = _small_dense()
+    eng.set_dense(x)
+    eng.set_doc_meta(SN, None, None)
+    q = np.ascontiguousarray(base[np.arange(NQ) % NB])
+    bad, (ptr, rows, lo) = _malformed_lists()
+    for message, p_, r_, l_ in bad:
+        _refused(eng, DSTATS, lambda ids, sc, ln: eng._lib.erh_dense_topk_rows(
+            eng._h, q.ctypes.data, _lib.ERH_F16, 0, 0, NQ, 3, 2, p_.ctypes.data, r_.ctypes.data, l_.ctypes.data, ids.ctypes.data, sc.ctypes.data,
+            ln.ctypes.data, 0, 0), "erh_dense_topk_rows", message)
+    lists = [rows[:3000].astype(np.int64), rows[3000:].astype(np.int64)]
+    st = _stats(eng, DSTATS)
+    got = eng.dense_topk_rows_csr(q, 100, ptr, rows, lo)
+    assert _moved(eng, DSTATS, st)[0]["dense_rows_scan_calls"] == 1
+    _dense_check(got, S, lists, lo, 100, "valid after the refused calls")
+
+
+def test_bm25_error_strings_name_the_entry(eng):
+    c = _small_bm25()
+    idx, S = c["idx"], c["S"]
+    eng.set_bm25(idx)
+    dir_id = (np.arange(SN) * 4 // SN).astype(np.int16)
+    eng.set_doc_meta(SN, None, dir_id)
+    qi, qt = (np.ascontiguousarray(a, np.int32) for a in _csr(idx, c["queries"]))
+    bad, (ptr, rows, lo) = _malformed_lists()
+
+    def rows_call(qi_, qt_, p_, r_, l_):
+        return lambda ids, sc, ln: eng._lib.erh_bm25_topk_rows(
+            eng._h, qi_.ctypes.data, qt_.ctypes.data, NQ, 3, 2, p_.ctypes.data, r_.ctypes.data, l_.ctypes.data, ids.ctypes.data, sc.ctypes.data,
+            ln.ctypes.data, 0, 0)
+
+    set_ptr, set_cls = eng.sets_to_csr([[b % 4, (b + 1) % 4] for b in range(NQ)], NQ)
+
+    def sets_call(qi_, qt_):
+        return lambda ids, sc, ln: eng._lib.erh_bm25_topk_sets(
+            eng._h, qi_.ctypes.data, qt_.ctypes.data, NQ, 3, set_ptr.ctypes.data, set_cls.ctypes.data, ids.ctypes.data, sc.ctypes.data,
+            ln.ctypes.data, 0, 0)
+
+    for message, p_, r_, l_ in bad:
+        _refused(eng, BSTATS, rows_call(qi, qt, p_, r_, l_), "erh_bm25_topk_rows", message)
+    # the query CSR, shared with erh_bm25_topk_sets: each entry under its own name
+    down, past = qi.copy(), qt.copy()
+    down[3] = down[2] - 1
+    past[int(qi[NQ]) - 1] = idx.n_vocab
+    sets_stats = BSTATS + ("bm25_calls", "bm25_sets_calls", "bm25_sets_subqueries")
+    for message, qi_, qt_ in (("q_indptr must be non-decreasing", down, qt), ("query term id out of range", qi, past)):
+        _refused(eng, BSTATS, rows_call(qi_, qt_, ptr, rows, lo), "erh_bm25_topk_rows", message)
+        _refused(eng, sets_stats, sets_call(qi_, qt_), "erh_bm25_topk_sets", message)
+    # valid calls on the same handle
+    lists = [rows[:3000].astype(np.int64), rows[3000:].astype(np.int64)]
+    st = _stats(eng, BSTATS)
+    got = eng.bm25_topk_rows_csr(qi, qt, 50, ptr, rows, lo)
+    assert _moved(eng, BSTATS, st)[0]["bm25_rows_scan_calls"] == 1
+    _bm25_check(got, lambda b: S[b], lists, lo, 50, "valid after the refused calls")
+    ids, sc, ln = eng.bm25_topk_sets(qi, qt, 50, [[b % 4, (b + 1) % 4] for b in range(NQ)])
+    for b in range(NQ):
+        oid, osc = _bm25_rank(S[b], np.flatnonzero((dir_id == b % 4) | (dir_id == (b + 1) % 4)), 50)
+        assert ln[b] == len(oid) and np.array_equal(ids[b, :ln[b]], oid) and np.array_equal(_bits(sc[b, :ln[b]]), _bits(osc)), b
+    eng.set_doc_meta(SN, None, None)
+
+
 # ---- the retrievers get the route for free ------------------------------------------------------------------------------------------------
 def test_hybrid_retriever_on_one_long_list():
     import zlib
