@@ -16,7 +16,7 @@ MEASURE = os.environ.get("ERH_MEASURE", "0") not in ("", "0")
 LIB_PATH = PKG_DIR / ("libeasyrag_hip_measure.so" if MEASURE else "libeasyrag_hip.so")
 STAMP = PKG_DIR / (".libeasyrag_hip_measure.stamp" if MEASURE else ".libeasyrag_hip.stamp")
 
-SOURCES = ["api.hip", "rows_entries.hip", "pipeline_dense.hip", "pipeline_bm25.hip", "comm.hip", "dense_scan.hip", "dense_gemv.hip", "select.hip", "dense_sets.hip", "dense_rows.hip", "bm25.hip", "bm25_rows.hip", "bm25_sets.hip", "rows_classes.hip", "fuse.hip", "shard_merge.hip", "index_build.hip", "text.hip"]
+SOURCES = ["api.hip", "rows_entries.hip", "exclude_entries.hip", "pipeline_dense.hip", "pipeline_bm25.hip", "comm.hip", "dense_scan.hip", "dense_gemv.hip", "select.hip", "dense_sets.hip", "dense_rows.hip", "bm25.hip", "bm25_rows.hip", "bm25_sets.hip", "rows_classes.hip", "exclude.hip", "fuse.hip", "shard_merge.hip", "index_build.hip", "text.hip"]
 HEADERS = ["common.h", "kernels.h", "handle.h"]
 # kernel generations that compile only into the measurement build (scripts/kbench.py): part of ITS digest, not of the product's
 MEASURE_ONLY = ["measure/dense_scan_persist.inc", "measure/dense_scan_pp12.inc", "measure/dense_scan_pp4.inc"]

@@ -260,6 +260,61 @@ int bm25_sets_run(erh_handle *h, const char *who, const int32_t *q_indptr, const
     return ERH_OK;
 }
 
+// ... and with the exclude entries (exclude_entries.hip) as well: the query block's staging, the class-set CSR and its sub-query batch
+int stage_query_block(erh_handle *h, const void *q, int q_dtype, int q_is_device, int B, hipStream_t st, const void **dev) {
+    if (q_is_device) { *dev = q; return ERH_OK; }
+    const size_t bytes = (size_t)B * h->d * (q_dtype == ERH_F16 ? 2 : 4);
+    HIPCHK(h, h->qin.ensure(bytes));
+    HIPCHK(h, hipMemcpyAsync(h->qin.p, q, bytes, hipMemcpyHostToDevice, st));
+    *dev = h->qin.p;
+    return ERH_OK;
+}
+
+// The class-set CSR of the two sets entries (erh_dense_topk_sets, erh_bm25_topk_sets): monotone from 0, classes >= 0 (32767 = matches
+// nothing) and distinct within a set, or the set {-1} alone; a set that names a class needs a class column over all n_docs documents.
+int check_class_sets(erh_handle *h, const char *who, const int32_t *set_ptr, const int16_t *set_cls, int B, int64_t n_docs) {
+    const std::string w(who);
+    if (set_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, (w + ": set_ptr[0] != 0").c_str());
+    for (int b = 0; b < B; ++b)
+        if (set_ptr[b + 1] < set_ptr[b]) return h->fail(ERH_ERR_INVALID, (w + ": set_ptr not monotone").c_str());
+    if (set_ptr[B] > 0 && !set_cls) return h->fail(ERH_ERR_INVALID, (w + ": null set_cls").c_str());
+    bool any_class = false;
+    std::vector<int16_t> tmp;
+    for (int b = 0; b < B; ++b) {
+        const int m = set_ptr[b + 1] - set_ptr[b];
+        const int16_t *c = set_cls + set_ptr[b];
+        if (m == 1 && c[0] == -1) continue;
+        tmp.assign(c, c + m);
+        std::sort(tmp.begin(), tmp.end());
+        for (int i = 0; i < m; ++i) {
+            if (tmp[i] < 0) return h->fail(ERH_ERR_INVALID, (w + ": negative class (only the set {-1} means unfiltered)").c_str());
+            if (i && tmp[i] == tmp[i - 1]) return h->fail(ERH_ERR_INVALID, (w + ": a class twice in one set").c_str());
+        }
+        any_class = any_class || m > 0;
+    }
+    if (any_class && (!h->has_dir || h->Nmeta < n_docs))
+        return h->fail(ERH_ERR_STATE, (w + ": set filter given but erh_set_doc_meta(dir_id) not set for all documents").c_str());
+    return ERH_OK;
+}
+
+// ... and its sub-query batch: source query and class of every sub-query, query b's sub-queries at sub_ptr[b] .. sub_ptr[b + 1].  A class
+// that no document carries (32767, or beyond the classes erh_set_doc_meta saw) contributes nothing and gets no sub-query; an unfiltered
+// query gets one without a class.
+void expand_class_sets(const erh_handle *h, const int32_t *set_ptr, const int16_t *set_cls, int B, std::vector<int32_t> &sub_ptr,
+                       std::vector<int32_t> &src, std::vector<int16_t> &cls) {
+    const int nc = (int)h->dir_cnt_h.size();
+    sub_ptr.assign((size_t)B + 1, 0);
+    for (int b = 0; b < B; ++b) {
+        const int m = set_ptr[b + 1] - set_ptr[b];
+        const int16_t *c = set_cls ? set_cls + set_ptr[b] : nullptr;
+        if (m == 1 && c[0] == -1) { src.push_back(b); cls.push_back(-1); }
+        else
+            for (int i = 0; i < m; ++i)
+                if (c[i] < nc && h->dir_cnt_h[c[i]] > 0) { src.push_back(b); cls.push_back(c[i]); }
+        sub_ptr[(size_t)b + 1] = (int32_t)src.size();
+    }
+}
+
 extern "C" {
 
 int erh_version(void) { return 200; }
@@ -438,7 +493,8 @@ int erh_get_stat(erh_handle *h, const char *name, int64_t *value) {
         {"bm25_sets_calls", T.bm25_sets_calls}, {"bm25_sets_subqueries", T.bm25_sets_subqueries},
         {"bm25_sets_merge_launches", T.bm25_sets_merge_launches},
         {"dense_rows_scan_calls", T.dense_rows_scan_calls}, {"dense_rows_scan_subqueries", T.dense_rows_scan_subqueries},
-        {"bm25_rows_scan_calls", T.bm25_rows_scan_calls}, {"bm25_rows_scan_subqueries", T.bm25_rows_scan_subqueries}};
+        {"bm25_rows_scan_calls", T.bm25_rows_scan_calls}, {"bm25_rows_scan_subqueries", T.bm25_rows_scan_subqueries},
+        {"dense_excl_calls", T.dense_excl_calls}, {"bm25_excl_calls", T.bm25_excl_calls}, {"excl_drop_launches", T.excl_drop_launches}};
     for (const auto &e : host)
         if (!strcmp(name, e.n)) { *value = e.v; return ERH_OK; }
     if (!strcmp(name, "dense_candidates_last_call")) {
@@ -1035,15 +1091,6 @@ static int stage_filter(erh_handle *h, const int16_t *filter_dir, int B, int64_t
     return ERH_OK;
 }
 
-static int stage_query_block(erh_handle *h, const void *q, int q_dtype, int q_is_device, int B, hipStream_t st, const void **dev) {
-    if (q_is_device) { *dev = q; return ERH_OK; }
-    const size_t bytes = (size_t)B * h->d * (q_dtype == ERH_F16 ? 2 : 4);
-    HIPCHK(h, h->qin.ensure(bytes));
-    HIPCHK(h, hipMemcpyAsync(h->qin.p, q, bytes, hipMemcpyHostToDevice, st));
-    *dev = h->qin.p;
-    return ERH_OK;
-}
-
 int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
                    int B, int k, const int16_t *filter_dir, int mode,
                    int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream) {
@@ -1072,51 +1119,6 @@ int erh_dense_topk(erh_handle *h, const void *q, int q_dtype, int q_is_device, i
 // kSetsChunk sub-queries when the batch is larger: every chunk but the last is checked before the next one reuses the work space), then
 // one merge launch (dense_sets.hip) builds each query's list from its sub-lists.  An unfiltered query ({-1}) is one sub-query without a
 // class, an empty set none.  erh_dense_check -> dense_sets_check: the sub-queries' flag words, and the merge again if they changed a list.
-
-// The class-set CSR of the two sets entries (erh_dense_topk_sets, erh_bm25_topk_sets): monotone from 0, classes >= 0 (32767 = matches
-// nothing) and distinct within a set, or the set {-1} alone; a set that names a class needs a class column over all n_docs documents.
-static int check_class_sets(erh_handle *h, const char *who, const int32_t *set_ptr, const int16_t *set_cls, int B, int64_t n_docs) {
-    const std::string w(who);
-    if (set_ptr[0] != 0) return h->fail(ERH_ERR_INVALID, (w + ": set_ptr[0] != 0").c_str());
-    for (int b = 0; b < B; ++b)
-        if (set_ptr[b + 1] < set_ptr[b]) return h->fail(ERH_ERR_INVALID, (w + ": set_ptr not monotone").c_str());
-    if (set_ptr[B] > 0 && !set_cls) return h->fail(ERH_ERR_INVALID, (w + ": null set_cls").c_str());
-    bool any_class = false;
-    std::vector<int16_t> tmp;
-    for (int b = 0; b < B; ++b) {
-        const int m = set_ptr[b + 1] - set_ptr[b];
-        const int16_t *c = set_cls + set_ptr[b];
-        if (m == 1 && c[0] == -1) continue;
-        tmp.assign(c, c + m);
-        std::sort(tmp.begin(), tmp.end());
-        for (int i = 0; i < m; ++i) {
-            if (tmp[i] < 0) return h->fail(ERH_ERR_INVALID, (w + ": negative class (only the set {-1} means unfiltered)").c_str());
-            if (i && tmp[i] == tmp[i - 1]) return h->fail(ERH_ERR_INVALID, (w + ": a class twice in one set").c_str());
-        }
-        any_class = any_class || m > 0;
-    }
-    if (any_class && (!h->has_dir || h->Nmeta < n_docs))
-        return h->fail(ERH_ERR_STATE, (w + ": set filter given but erh_set_doc_meta(dir_id) not set for all documents").c_str());
-    return ERH_OK;
-}
-
-// ... and its sub-query batch: source query and class of every sub-query, query b's sub-queries at sub_ptr[b] .. sub_ptr[b + 1].  A class
-// that no document carries (32767, or beyond the classes erh_set_doc_meta saw) contributes nothing and gets no sub-query; an unfiltered
-// query gets one without a class.
-static void expand_class_sets(const erh_handle *h, const int32_t *set_ptr, const int16_t *set_cls, int B, std::vector<int32_t> &sub_ptr,
-                              std::vector<int32_t> &src, std::vector<int16_t> &cls) {
-    const int nc = (int)h->dir_cnt_h.size();
-    sub_ptr.assign((size_t)B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-        const int m = set_ptr[b + 1] - set_ptr[b];
-        const int16_t *c = set_cls ? set_cls + set_ptr[b] : nullptr;
-        if (m == 1 && c[0] == -1) { src.push_back(b); cls.push_back(-1); }
-        else
-            for (int i = 0; i < m; ++i)
-                if (c[i] < nc && h->dir_cnt_h[c[i]] > 0) { src.push_back(b); cls.push_back(c[i]); }
-        sub_ptr[(size_t)b + 1] = (int32_t)src.size();
-    }
-}
 
 int erh_dense_topk_sets(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q,
                         int B, int k, const int32_t *set_ptr, const int16_t *set_cls, int mode,

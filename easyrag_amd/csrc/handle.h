@@ -229,6 +229,10 @@ struct erh_handle {
     // erh_bm25_topk_sets (bm25_sets.hip): the sub-queries' lists [n_sub x k] that its class-column scans write and its merge reads, and
     // bs_tab: sub_ptr int32[B + 1], one upload per call.  The scans themselves use what erh_bm25_topk uses (qpack, part_*).
     DevBuf bs_tab, bs_ids, bs_sc, bs_len;
+    // erh_dense_topk_excl / erh_bm25_topk_excl (exclude_entries.hip, DESIGN K12), one set of buffers per route: tab = the call's exclusion
+    // CSR (excl_ptr int32[B + 1] | excl_ids), one upload; ids / sc / len = the over-fetched lists [B x kk] that the route's sets pipeline
+    // writes and the drop kernel (exclude.hip) reads.  The next call of the route reuses them in stream order.
+    struct ExclBufs { DevBuf tab, ids, sc, len; } xd, xb;
     // The rows entries (rows_entries.hip), one set of buffers per route (the two corpora may differ in size); the next call of the route
     // reuses them in stream order.  rows: the call's row ids, every call's, copied straight from the caller's array -- read by the
     // row-by-row shapes and by the classification alike, whichever of them the call ends up on.  The rest is the scan route's (rows_classes.hip,
@@ -303,7 +307,7 @@ struct erh_handle {
                 dense_group_reruns = 0, bm25_rows_calls = 0, bm25_rows_short = 0, bm25_rows_long = 0,
                 bm25_sets_calls = 0, bm25_sets_subqueries = 0, bm25_sets_merge_launches = 0,
                 dense_rows_scan_calls = 0, dense_rows_scan_subqueries = 0, bm25_rows_scan_calls = 0, bm25_rows_scan_subqueries = 0,
-                dense_block_builds = 0;
+                dense_block_builds = 0, dense_excl_calls = 0, bm25_excl_calls = 0, excl_drop_launches = 0;
     } stats;
     // multi-GPU exchange (erh_comm_* / erh_allgather_topk): RCCL communicator + packed send / receive rows
     void *comm = nullptr;
@@ -486,6 +490,11 @@ int dense_sets_check(erh_handle *h, hipStream_t st);   // erh_dense_check after 
 // of a set-filtered call behind its validation, which their scan route runs on a call-local class column.
 int check_dense_args(erh_handle *h, const char *who, const void *q, bool outs, int B, int k, int q_dtype, int mode);
 int check_bm25_queries(erh_handle *h, const char *who, const int32_t *q_indptr, const int32_t *q_tok, int B, int64_t V);
+// ... and with the exclude entries (exclude_entries.hip): the class-set CSR of a sets call, its sub-query batch, the query block's staging
+int check_class_sets(erh_handle *h, const char *who, const int32_t *set_ptr, const int16_t *set_cls, int B, int64_t n_docs);
+void expand_class_sets(const erh_handle *h, const int32_t *set_ptr, const int16_t *set_cls, int B, std::vector<int32_t> &sub_ptr,
+                       std::vector<int32_t> &src, std::vector<int16_t> &cls);
+int stage_query_block(erh_handle *h, const void *q, int q_dtype, int q_is_device, int B, hipStream_t st, const void **dev);
 int dense_sets_run(erh_handle *h, const void *qd, int q_dtype, int normalize_q, int B, int k, const std::vector<int32_t> &sub_ptr,
                    const std::vector<int32_t> &src, const std::vector<int16_t> &cls, int mode, int32_t *d_ids, double *d_sc, int32_t *d_len,
                    hipStream_t st);

@@ -401,4 +401,12 @@ size_t rows_classes_table_bytes(int slots, int max_cells); // header (16 bytes: 
 hipError_t launch_rows_classes(const int32_t *rows, const int64_t *routed, int n_routed, int64_t max_len, int64_t N, int slots, int max_cells,
                                unsigned long long *sig, void *table, int16_t *cls, hipStream_t st);
 
+// ---- exclude.hip: exclude lists (erh_dense_topk_excl / erh_bm25_topk_excl, DESIGN K12) ---------------------------------------------------
+constexpr int kTopkDropMaxDepth = 1024;    // deepest over-fetched list (erh_bm25_topk's limit on k)
+// in_* [B x kk] with in_len[b] valid entries (canonical order); excl_ptr int32[B + 1], excl_ids strictly ascending per query (device).  out
+// row b = the first k entries of in row b whose id is not in query b's exclusion list, in order, scores copied as bits, padded with id -1 /
+// score 0; out_len[b] = min(k, survivors).  1 <= k <= kk <= kTopkDropMaxDepth; in and out rows must not overlap.
+hipError_t launch_topk_drop(const int32_t *in_ids, const double *in_sc, const int32_t *in_len, int kk, const int32_t *excl_ptr,
+                            const int32_t *excl_ids, int B, int k, int32_t *out_ids, double *out_sc, int32_t *out_len, hipStream_t st);
+
 }  // namespace erh

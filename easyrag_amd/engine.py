@@ -385,6 +385,80 @@ class RetrievalEngine:
                                                   1 if device_out else 0, self._stream(stream)))
         return ids, sc, ln
 
+    @staticmethod
+    def excl_to_csr(excl, B: int) -> Tuple[np.ndarray, np.ndarray]:
+        """One exclusion list per query (a sequence or array of ids, or None = nothing excluded; `excl` itself None = no query
+        excludes anything) -> (excl_ptr int32[B+1], excl_ids int32[...]), every list sorted and de-duplicated.  Ids must be
+        integers that fit int32 and are >= 0; the library checks them against N."""
+        if excl is None:
+            excl = [None] * B
+        if len(excl) != B:
+            raise ValueError("exclude must have one entry per query")
+        arrs = []
+        for e in excl:
+            a = np.zeros(0, np.int64) if e is None else np.asarray(e).reshape(-1)
+            if a.size and a.dtype.kind not in "iu":
+                raise ValueError("excluded ids must be integers")
+            a = np.unique(a.astype(np.int64))
+            if a.size and (a[0] < 0 or a[-1] >= 2**31):
+                raise ValueError("excluded ids must lie in [0, 2^31)")
+            arrs.append(a)
+        ptr = np.zeros(B + 1, np.int64)
+        if arrs:
+            np.cumsum([a.size for a in arrs], out=ptr[1:])
+        if ptr[-1] >= 2**31:
+            raise ValueError("more than 2^31 excluded ids in one call")
+        ids = np.concatenate(arrs) if arrs else np.zeros(0, np.int64)
+        return ptr.astype(np.int32), np.ascontiguousarray(ids, dtype=np.int32)
+
+    def dense_topk_excl(self, q, k: int, exclude, sets=None, mode: int = _lib.ERH_DENSE_EXACT, normalize_q: bool = False,
+                        device_out: bool = False, stream=None):
+        """Dense top-k of what query b may see (sets[b] as in dense_topk_sets; sets None: everything) except the ids exclude[b]
+        (erh_dense_topk_excl).  k + the longest exclusion list must be <= 768.  device_out: results are final after sync() -- no
+        dense_check() is needed."""
+        q, dt, is_dev, B = self._q_desc(q)
+        return self.dense_topk_excl_csr(q, k, *self.excl_to_csr(exclude, B), sets=sets, mode=mode, normalize_q=normalize_q,
+                                        device_out=device_out, stream=stream)
+
+    def dense_topk_excl_csr(self, q, k: int, eptr, eids, sets=None, mode: int = _lib.ERH_DENSE_EXACT, normalize_q: bool = False,
+                            device_out: bool = False, stream=None):
+        """dense_topk_excl on the C entry's own tables (excl_to_csr's result): a caller that sends the same lists again builds them once."""
+        q, dt, is_dev, B = self._q_desc(q)
+        eptr, eids = _np(eptr, np.int32), _np(eids, np.int32)
+        if eptr.shape[0] != B + 1:
+            raise ValueError("excl_ptr must have one entry per query and one more")
+        ptr, cls = (None, None) if sets is None else self.sets_to_csr(sets, B)
+        ids, sc, ln = self._outs(B, k, device_out)
+        self._check(self._lib.erh_dense_topk_excl(self._h, _ptr(q), dt, is_dev, 1 if normalize_q else 0, B, int(k), _ptr(ptr), _ptr(cls),
+                                                  _ptr(eptr), _ptr(eids), int(mode), _ptr(ids), _ptr(sc), _ptr(ln),
+                                                  1 if device_out else 0, self._stream(stream)))
+        return ids, sc, ln
+
+    def bm25_topk_excl(self, q_indptr, q_tok, k: int, exclude, sets=None, slot: Optional[int] = None, device_out: bool = False,
+                       stream=None):
+        """BM25 top-k of what query b may see (sets[b] as in bm25_topk_sets; sets None: everything) except the ids exclude[b]
+        (erh_bm25_topk_excl).  k + the longest exclusion list must be <= 1024.  device_out: results are final after sync()."""
+        B = int(np.asarray(q_indptr).shape[0]) - 1
+        return self.bm25_topk_excl_csr(q_indptr, q_tok, k, *self.excl_to_csr(exclude, B), sets=sets, slot=slot, device_out=device_out,
+                                       stream=stream)
+
+    def bm25_topk_excl_csr(self, q_indptr, q_tok, k: int, eptr, eids, sets=None, slot: Optional[int] = None, device_out: bool = False,
+                           stream=None):
+        """bm25_topk_excl on the C entry's own tables (excl_to_csr's result)."""
+        self._select(slot)
+        q_indptr = _np(q_indptr, np.int32)
+        q_tok = _np(q_tok, np.int32)
+        B = q_indptr.shape[0] - 1
+        eptr, eids = _np(eptr, np.int32), _np(eids, np.int32)
+        if eptr.shape[0] != B + 1:
+            raise ValueError("excl_ptr must have one entry per query and one more")
+        ptr, cls = (None, None) if sets is None else self.sets_to_csr(sets, B)
+        ids, sc, ln = self._outs(B, k, device_out)
+        self._check(self._lib.erh_bm25_topk_excl(self._h, _ptr(q_indptr), _ptr(q_tok), B, int(k), _ptr(ptr), _ptr(cls), _ptr(eptr),
+                                                 _ptr(eids), _ptr(ids), _ptr(sc), _ptr(ln), 1 if device_out else 0,
+                                                 self._stream(stream)))
+        return ids, sc, ln
+
     def bm25_topk(self, q_indptr, q_tok, k: int, filter_dir=None, device_out: bool = False, stream=None,
                   slot: Optional[int] = None):
         self._select(slot)
@@ -658,7 +732,7 @@ class RetrievalEngine:
                   "bm25_rows_calls", "bm25_rows_short_launches", "bm25_rows_long_launches",
                   "bm25_sets_calls", "bm25_sets_subqueries", "bm25_sets_merge_launches",
                   "dense_rows_scan_calls", "dense_rows_scan_subqueries", "bm25_rows_scan_calls", "bm25_rows_scan_subqueries",
-                  "dense_block_builds",
+                  "dense_block_builds", "dense_excl_calls", "bm25_excl_calls", "excl_drop_launches",
                   "hybrid_lazy_queries", "dense_rescored_rows_last_call")
 
     def stat(self, name: str) -> int:

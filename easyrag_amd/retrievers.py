@@ -211,6 +211,10 @@ def _bound(v, where: str):
 def _compile_condition(c, keys: set):
     """One condition -> a hashable tree node; `keys` collects the metadata keys it mentions."""
     name = type(c).__name__
+    if hasattr(c, "has_id"):                                       # HasIdCondition: no payload condition (see _lift_id_conditions)
+        raise TypeError(f"unsupported place for {name}: a HasIdCondition is served directly inside the top-level must (a rows= list) or "
+                        f"must_not (an exclusion) of a retriever's filter, nowhere else: {c!r}")
+    name = type(c).__name__
     if hasattr(c, "key"):                                          # FieldCondition
         key = c.key
         if not isinstance(key, str) or "." in key or "[" in key:
@@ -583,6 +587,136 @@ def _node_positions(holder, nodes, nodes_or_ids, owner: str) -> np.ndarray:
     return np.unique(np.asarray(ids, np.int64))
 
 
+# ---------------------------------------------------------------------------------------------------
+# Exclude lists (DESIGN K12): `exclude=` of the retrievers and must_not: [HasIdCondition] of their filters.
+def plan_exclusion(k: int, e_max: int, limit: int) -> str:
+    """Which route serves top k minus an exclusion list of e_max ids on a route whose depth limit is `limit`: "drop" -- the route's
+    pipeline at depth k + e_max and the drop kernel (erh_*_topk_excl) -- when that depth fits, else "complement": the allowed rows
+    without the excluded ones as a rows= list (erh_*_topk_rows).  The result is the same either way."""
+    return "drop" if int(k) + int(e_max) <= int(limit) else "complement"
+
+
+def _id_positions(holder, nodes, entry, owner: str) -> np.ndarray:
+    """Positions in `nodes` of one exclude / HasIdCondition entry -- positions, node ids (strings), node objects or NodeWithScore, in
+    any mixture --, ascending and distinct.  The node id -> position map is built on first use and kept on `holder`."""
+    if entry is None:
+        return np.zeros(0, np.int64)
+    if isinstance(entry, np.ndarray):
+        entry = entry.reshape(-1).tolist() if entry.dtype.kind in "iu" else list(entry.reshape(-1))
+    elif isinstance(entry, (str, bytes)) or not hasattr(entry, "__iter__"):
+        entry = [entry]
+    out, objs = [], []
+    for x in entry:
+        if isinstance(x, str):
+            by_id = holder.__dict__.get("_position_of_id")
+            if by_id is None:
+                by_id = holder.__dict__["_position_of_id"] = {n.node_id: i for i, n in enumerate(nodes)}
+            if x not in by_id:
+                raise ValueError(f"exclude: node id {x!r} is not part of this {owner}'s node list")
+            out.append(by_id[x])
+        elif isinstance(x, (int, np.integer)) and not isinstance(x, bool):
+            if not 0 <= int(x) < len(nodes):
+                raise ValueError(f"exclude: positions must lie in [0, {len(nodes)})")
+            out.append(int(x))
+        else:
+            objs.append(x)
+    pos = np.asarray(out, np.int64)
+    if objs:
+        pos = np.concatenate([pos, _node_positions(holder, nodes, objs, owner)])
+    return np.unique(pos)
+
+
+def _per_query_exclude(exclude, B: int, resolve) -> Optional[List[np.ndarray]]:
+    """`exclude` (one entry for every query, or a list parallel to the queries of entries / None) -> per query an ascending,
+    duplicate-free position array; None when nothing is given.  `resolve(entry)` is _id_positions on the caller's nodes."""
+    if exclude is None:
+        return None
+    per_query = (isinstance(exclude, (list, tuple)) and len(exclude) == B
+                 and all(e is None or (hasattr(e, "__len__") and not isinstance(e, (str, bytes))) for e in exclude))
+    if per_query:
+        return [resolve(e) for e in exclude]
+    one = resolve(exclude)
+    return [one] * B
+
+
+class _RestFilter:
+    """A Filter without its top-level id conditions: what the payload compiler (_filter_spec) gets."""
+
+    __slots__ = ("must", "should", "must_not", "min_should")
+
+    def __init__(self, must, should, must_not, min_should):
+        self.must, self.should, self.must_not, self.min_should = must, should, must_not, min_should
+
+
+def _split_id_conditions(f):
+    """One filter -> (the filter without the HasIdCondition entries of its top-level must / must_not, the ids every must entry lists
+    (None: no such entry), the ids any must_not entry lists (None: no such entry)).  A HasIdCondition anywhere else stays where it is
+    and the payload compiler raises its TypeError there."""
+    if f is None or isinstance(f, dict) or not any(hasattr(f, a) for a in ("must", "should", "must_not")):
+        return f, None, None
+    must, must_not = _clause(getattr(f, "must", None)), _clause(getattr(f, "must_not", None))
+    inc = [c for c in must if hasattr(c, "has_id")]
+    exc = [c for c in must_not if hasattr(c, "has_id")]
+    if not inc and not exc:
+        return f, None, None
+    rest = _RestFilter([c for c in must if not hasattr(c, "has_id")], getattr(f, "should", None),
+                       [c for c in must_not if not hasattr(c, "has_id")], getattr(f, "min_should", None))
+    return rest, ([list(_clause(c.has_id)) for c in inc] or None), ([x for c in exc for x in _clause(c.has_id)] if exc else None)
+
+
+def _has_id_conditions(filters) -> bool:
+    """Whether a filter (or one of a list of filters) carries a HasIdCondition in its top-level must / must_not."""
+    return any(_split_id_conditions(f)[1:] != (None, None) for f in (filters if isinstance(filters, (list, tuple)) else [filters]))
+
+
+def _lift_id_conditions(filters, rows, exclude, B: int, n: int, resolve):
+    """The HasIdCondition entries of a batch's filters moved to where they are served: must -> the query's rows= list (the ids every
+    entry lists; with a rows= argument as well: those of them), must_not -> its exclusion (with an exclude= argument as well: both).
+    Returns (filters, rows, exclude per query or None); a batch without id conditions gets its `filters` and `rows` back untouched."""
+    excl_q = _per_query_exclude(exclude, B, resolve)
+    per = list(filters) if isinstance(filters, (list, tuple)) and len(filters) == B else None
+    seen: Dict[int, tuple] = {}
+
+    def split(f):
+        hit = seen.get(id(f))
+        if hit is None:
+            hit = seen[id(f)] = (f, _split_id_conditions(f))     # (f is held, so its id stays its own for the batch)
+        return hit[1]
+    parts = [split(f) for f in (per if per is not None else [filters])]
+    if all(m is None and x is None for _, m, x in parts):
+        return filters, rows, excl_q
+    if per is None:
+        parts = parts * B
+    rows_q = _per_query_rows(rows, B, n)
+    if excl_q is None:
+        excl_q = [np.zeros(0, np.int64)] * B
+    excl_q = list(excl_q)
+    for b, (_, m, x) in enumerate(parts):
+        if m is not None:
+            for ids in m:
+                r = resolve(ids)
+                rows_q[b] = r if rows_q[b] is None else np.intersect1d(rows_q[b], r, assume_unique=True)
+        if x is not None:
+            excl_q[b] = np.union1d(excl_q[b], resolve(x))
+    return [rest for rest, _, _ in parts], (rows_q if any(r is not None for r in rows_q) else None), excl_q
+
+
+def _without(rows: np.ndarray, excl: np.ndarray) -> np.ndarray:
+    return rows if excl.size == 0 else rows[~np.isin(rows, excl)]
+
+
+def _allowed_rows(corpus: "_FilteredCorpus", spec) -> np.ndarray:
+    """Ascending rows a query with filter `spec` (None, a dict, a _SetFilter) may see: the complement route's population."""
+    return np.arange(len(corpus.nodes), dtype=np.int64) if not spec else corpus.rows_matching(spec)
+
+
+def _plan_sets(plan: Sequence[Any]):
+    """corpus.plan's answers as the class sets of an erh_*_topk_excl call; None when no query is filtered."""
+    if all(not isinstance(c, list) and c == -1 for c in plan):
+        return None
+    return [None if (not isinstance(c, list) and c == -1) else (c if isinstance(c, list) else [c]) for c in plan]
+
+
 def _corpus_for(nodes, engine: Optional[RetrievalEngine]) -> _FilteredCorpus:
     """Retrievers built over the same engine share one _FilteredCorpus (and so one metadata upload).  The
     bookkeeping lives on the engine object (no process-global cache pinning engines); an engine serves ONE node
@@ -809,11 +943,15 @@ class HipVectorStore:
 
     rows_route_max = 0     # > 0: a filtered query whose filter allows at most this many rows goes through the rows entry (opt-in; results identical)
 
-    def query_batch(self, query_embeddings, similarity_top_k: int, filters=None, mode: int = _lib.ERH_DENSE_EXACT, rows=None):
+    def query_batch(self, query_embeddings, similarity_top_k: int, filters=None, mode: int = _lib.ERH_DENSE_EXACT, rows=None,
+                    exclude=None):
         """`filters`: one filter for the whole batch (None, dict, qdrant Filter) or a list with one filter per query.
         `rows`: restrict queries to explicit row ids (positions in the node list) -- one id array for every query, or a list parallel to
         the queries whose entries are an id array or None.  Such a query ranks exactly those rows (erh_dense_topk_rows; with a filter as
-        well: the rows that also pass it), the others run as without the argument, and the two parts are scattered into one result."""
+        well: the rows that also pass it), the others run as without the argument, and the two parts are scattered into one result.
+        `exclude`: node positions a query must NOT return -- one array for every query, or a list parallel to the queries of arrays /
+        None: the top k of (what the filter and rows allow) minus those (erh_dense_topk_excl, or the complement as a rows list where
+        k + the list's length exceeds the call's depth: plan_exclusion)."""
         q = _unit_f16(query_embeddings)
         B, k = q.shape[0], int(similarity_top_k)
         if not 1 <= k <= DENSE_MAX_K:
@@ -823,6 +961,9 @@ class HipVectorStore:
             raise ValueError("rows= ranks by the pinned fp64 score of every listed row: ERH_DENSE_EXACT only")
         dicts = _per_query(filters, B, _spec_cache())
         rows_q, dicts = self._resolve_rows(dicts, rows, B, mode)
+        excl_q = _per_query_exclude(exclude, B, lambda e: _id_positions(self, self.corpus.nodes, e, "store"))
+        if excl_q is not None and any(e.size for e in excl_q):
+            return self._query_excluding(q, k, dicts, rows_q, excl_q, mode)
         with_rows = [b for b in range(B) if rows_q[b] is not None]
         if not with_rows:
             return self._query_filtered(q, k, dicts, mode)
@@ -833,6 +974,34 @@ class HipVectorStore:
         rest = [b for b in range(B) if rows_q[b] is None]
         ids[rest], sc[rest], ln[rest] = self._query_filtered(q[rest], k, [dicts[b] for b in rest], mode)
         ids[with_rows], sc[with_rows], ln[with_rows] = self.engine.dense_topk_rows(q[with_rows], k, lists, list_of=list_of)
+        return ids, sc, ln
+
+    def _query_excluding(self, q, k: int, dicts, rows_q, excl_q, mode: int):
+        """The batch with exclusion lists.  A query with rows ranks its rows without the excluded ones; any other takes the drop route
+        (erh_dense_topk_excl, the filter as the call's class sets) when k + its exclusions fit the call's depth, else the complement
+        route: the rows its filter allows without the excluded ones, as a rows list."""
+        B = q.shape[0]
+        rows_q = list(rows_q)
+        drop: List[int] = []
+        for b in range(B):
+            if rows_q[b] is not None:
+                rows_q[b] = _without(rows_q[b], excl_q[b])
+            elif plan_exclusion(k, excl_q[b].size, DENSE_MAX_K) == "drop":
+                drop.append(b)
+            else:
+                if mode != _lib.ERH_DENSE_EXACT:
+                    raise ValueError(f"an exclusion list of {excl_q[b].size} ids with k = {k} exceeds the depth of erh_dense_topk_excl "
+                                     f"({DENSE_MAX_K}) and takes the rows route: ERH_DENSE_EXACT only")
+                rows_q[b] = _without(_allowed_rows(self.corpus, dicts[b]), excl_q[b])
+        ids, sc, ln = np.full((B, k), -1, np.int32), np.zeros((B, k), np.float64), np.zeros(B, np.int32)
+        for g in _by_key_set([dicts[b] for b in drop]):
+            g = [drop[j] for j in g]
+            sets = _plan_sets(self.corpus.plan([dicts[b] for b in g]))
+            ids[g], sc[g], ln[g] = self.engine.dense_topk_excl(q[g], k, [excl_q[b] for b in g], sets=sets, mode=mode)
+        with_rows = [b for b in range(B) if rows_q[b] is not None]
+        if with_rows:
+            lists, list_of = self._rows_lists([rows_q[b] for b in with_rows])
+            ids[with_rows], sc[with_rows], ln[with_rows] = self.engine.dense_topk_rows(q[with_rows], k, lists, list_of=list_of)
         return ids, sc, ln
 
     def _per_query_rows(self, rows, B: int) -> List[Optional[np.ndarray]]:
@@ -966,15 +1135,21 @@ class QdrantRetriever(_RetrieverBase):
         nodes, sims = self._vector_store.query(emb, self._similarity_top_k, self.filters)
         return [NodeWithScore(node=n, score=s) for n, s in zip(nodes, sims)]
 
-    def retrieve_batch(self, queries: Sequence[str], filters=_UNSET, rows=None) -> List[List[NodeWithScore]]:
+    def retrieve_batch(self, queries: Sequence[str], filters=_UNSET, rows=None, exclude=None) -> List[List[NodeWithScore]]:
         """`_retrieve` for a batch.  `filters` (default: the `filters` attribute, for every query) may be a list parallel to
         `queries`: one qdrant Filter / dict / None per question, as the reference's evaluation loop sets them one at a time.
-        `rows`: HipVectorStore.query_batch's argument -- node positions a query is restricted to (one array, or one array / None each)."""
+        `rows`: HipVectorStore.query_batch's argument -- node positions a query is restricted to (one array, or one array / None each).
+        `exclude`: what a query must NOT return -- one entry for every query, or a list parallel to the queries of entries / None; an
+        entry holds node positions, node ids, nodes or NodeWithScore.  A filter's must_not: [HasIdCondition(has_id=[...])] is the same
+        thing (ids: positions or node ids), its must: [HasIdCondition] a rows list; both combine with the arguments."""
         if len(queries) == 0:
             return []
+        store = self._vector_store
+        fl, rows, excl_q = _lift_id_conditions(self.filters if filters is _UNSET else filters, rows, exclude, len(queries),
+                                               len(store.nodes), lambda e: _id_positions(store, store.nodes, e, "store"))
         embs = np.asarray([self._embed_model.get_query_embedding(q) for q in queries], dtype=np.float32)
-        ids, sc, ln = self._vector_store.query_batch(embs, self._similarity_top_k,
-                                                     self.filters if filters is _UNSET else filters, rows=rows)
+        kw = {} if excl_q is None else {"exclude": excl_q}    # (a store without the argument keeps working for batches without exclusions)
+        ids, sc, ln = store.query_batch(embs, self._similarity_top_k, fl, rows=rows, **kw)
         nodes = self._vector_store.nodes
         return [[NodeWithScore(node=nodes[i], score=float(s)) for i, s in zip(ids[b, :ln[b]], sc[b, :ln[b]])]
                 for b in range(len(queries))]
@@ -1181,7 +1356,8 @@ class BM25Retriever(_RetrieverBase):
             ids[live], sc[live], ln[live] = self.engine.bm25_topk(qi, qt, k, slot=self._slot, filter_dir=col if np.any(col >= 0) else None)
         return ids, sc, ln
 
-    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, rows=None, filters=_UNSET) -> List[List[NodeWithScore]]:
+    def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, rows=None, filters=_UNSET,
+                       exclude=None) -> List[List[NodeWithScore]]:
         """get_scores + filter for a whole batch, fused on the GPU (no score vector leaves the chip).  `filter_dicts`
         (default: the `filter_dict` attribute, for every query) may be a list parallel to `queries`: one dict / None each.
         `filters` (default: the `filters` attribute): a Qdrant-style Filter -- MatchValue / MatchAny / MatchExcept / Range, must / should /
@@ -1191,17 +1367,31 @@ class BM25Retriever(_RetrieverBase):
         `rows`: restrict queries to explicit node positions -- one id array for every query, or a list parallel to the queries whose
         entries are an id array or None (HipVectorStore.query_batch's argument, normalised the same way).  Such a query ranks exactly
         those rows by the corpus index's BM25 (erh_bm25_topk_rows; with a filter as well: the rows that also pass it), the others
-        run as without the argument, and the two parts are scattered into one result."""
+        run as without the argument, and the two parts are scattered into one result.
+        `exclude`: QdrantRetriever.retrieve_batch's argument -- what a query must NOT return (positions, node ids, nodes or NodeWithScore;
+        one entry for every query or one each); must_not: [HasIdCondition] in `filters` is the same thing, must: [HasIdCondition] a rows
+        list.  Such a query takes erh_bm25_topk_excl when k + its exclusions fit the call's depth, else the complement as a rows list."""
         B = len(queries)
         if B == 0:
             return []
         dicts = _per_query(self.filter_dict if filter_dicts is _UNSET else filter_dicts, B, lambda v: dict(v) if v else None)
-        fl = self.filters if filters is _UNSET else filters
+        fl, rows, excl_q = _lift_id_conditions(self.filters if filters is _UNSET else filters, rows, exclude, B, len(self._nodes),
+                                               lambda e: _id_positions(self, self._nodes, e, "retriever"))
         if fl is not None:
             dicts = [_both(d, f) for d, f in zip(dicts, _per_query(fl, B, _spec_cache()))]
         tok = [self._query_ids(q) for q in queries]
         k = self._similarity_top_k
         rows_q, dicts = self._resolve_rows(dicts, rows, B)
+        drop: List[int] = []
+        if excl_q is not None and any(e.size for e in excl_q):
+            in_range = 1 <= k <= BM25_DEVICE_MAX_K
+            for b in range(B):
+                if rows_q[b] is not None:
+                    rows_q[b] = _without(rows_q[b], excl_q[b])
+                elif in_range and plan_exclusion(k, excl_q[b].size, BM25_DEVICE_MAX_K) == "drop":
+                    drop.append(b)
+                elif excl_q[b].size:
+                    rows_q[b], dicts[b] = _without(_allowed_rows(self._corpus_state, dicts[b]), excl_q[b]), None
         if not 1 <= k <= BM25_DEVICE_MAX_K:
             # outside the fused kernels' range (erh_bm25_topk: 1 <= k <= 1024) the reference's answer is still defined: the
             # score vector plus the host filter (restricted to the rows; a set filter as the rows it matches) give it exactly
@@ -1209,7 +1399,14 @@ class BM25Retriever(_RetrieverBase):
             return [self._filter_one(self._cast(self.engine.bm25_scores(t, slot=self._slot)), fd, k, rows=keep)
                     for t, (fd, keep) in zip(tok, masks)]
         out: List[List[NodeWithScore]] = [[] for _ in range(B)]
-        rest = [b for b in range(B) if rows_q[b] is None]
+        for g in _by_key_set([dicts[b] for b in drop]):
+            g = [drop[j] for j in g]
+            qi, qt = queries_to_csr([tok[b] for b in g])
+            ids, sc, ln = self.engine.bm25_topk_excl(qi, qt, k, [excl_q[b] for b in g],
+                                                     sets=_plan_sets(self._corpus_state.plan([dicts[b] for b in g])), slot=self._slot)
+            for j, b in enumerate(g):
+                out[b] = [NodeWithScore(node=self._nodes[i], score=float(s)) for i, s in zip(ids[j, :ln[j]], sc[j, :ln[j]])]
+        rest = [b for b in range(B) if rows_q[b] is None and b not in drop]
         for g in _by_key_set([dicts[b] for b in rest]):
             g = [rest[j] for j in g]
             if any(isinstance(dicts[b], _SetFilter) for b in g):
@@ -1398,7 +1595,7 @@ class HybridRetriever(_RetrieverBase):
         return self.retrieve_batch([query_bundle.query_str])[0]
 
     def retrieve_batch(self, queries: Sequence[str], filter_dicts=_UNSET, filters=_UNSET, rows=None,
-                       sparse_rows=None, sparse_filters=_UNSET) -> List[List[NodeWithScore]]:
+                       sparse_rows=None, sparse_filters=_UNSET, exclude=None) -> List[List[NodeWithScore]]:
         """`_aretrieve` for a batch of query strings.  Without the keyword arguments the `filter_dict` / `filters`
         attributes apply to every query and are pushed into the child retrievers as the reference does
         (retrievers.py:278,283).  `filter_dicts` (sparse route) / `filters` (dense route) may instead be lists parallel to
@@ -1410,13 +1607,19 @@ class HybridRetriever(_RetrieverBase):
         `sparse_filters` (not given: the sparse route gets its filter_dict only, as in the reference) hands the SPARSE route a Qdrant-style
         Filter as well (BM25Retriever.retrieve_batch's `filters`; one, or a list parallel to `queries`); the same object passed as
         `filters` and `sparse_filters` holds both routes to one population -- erh_bm25_topk_sets and erh_dense_topk_sets into device
-        buffers, then the RRF kernel."""
+        buffers, then the RRF kernel.
+        `exclude` (the child retrievers' argument; must_not: [HasIdCondition] in `filters` / `sparse_filters` adds to it, on its own
+        route) goes to BOTH routes, so the two lists are ranked over one population: erh_bm25_topk_excl and erh_dense_topk_excl into
+        device buffers, then the RRF kernel; where that composition does not apply, the routes on their own + RRF."""
         sp, de = self.sparse_retriever, self.dense_retriever
         B = len(queries)
         if B == 0:
             return []
         fs = self.filter_dict if filter_dicts is _UNSET else filter_dicts
         fdn = self.filters if filters is _UNSET else filters
+        if exclude is not None or _has_id_conditions(fdn) or (sparse_filters is not _UNSET and _has_id_conditions(sparse_filters)):
+            return self._retrieve_excluding(queries, fs, fdn, rows, sparse_rows, sparse_filters, exclude,
+                                            filter_dicts is _UNSET, filters is _UNSET)
         s_kw = {} if sparse_rows is None else {"rows": sparse_rows}
         if sparse_filters is not _UNSET:
             s_kw["filters"] = sparse_filters
@@ -1473,6 +1676,66 @@ class HybridRetriever(_RetrieverBase):
         ids, sc, ln = sp.engine.hybrid_topk(embs, qi, qt, k_dense=de._similarity_top_k,
                                             k_sparse=sp._similarity_top_k, K=60, topk=self.topk,
                                             filter_dir=filt_s, filter_dense=filt_d, slot=sp._slot)
+        nodes = sp._nodes
+        return [[NodeWithScore(node=nodes[i], score=float(s)) for i, s in zip(ids[b, :ln[b]], sc[b, :ln[b]])]
+                for b in range(B)]
+
+    def _retrieve_excluding(self, queries: Sequence[str], fs, fdn, rows, sparse_rows, sparse_filters, exclude,
+                            push_filter_dict: bool, push_filters: bool) -> List[List[NodeWithScore]]:
+        """retrieve_batch with `exclude`.  retrieval_type 3 on one engine, one key set, no row lists and every exclusion within both
+        routes' depths: erh_bm25_topk_excl and erh_dense_topk_excl into device buffers (the dense entry checks its inner call itself),
+        the RRF kernel over the two device lists, one synchronisation.  Anything else: the child retrievers with the exclusion + RRF."""
+        sp, de = self.sparse_retriever, self.dense_retriever
+        B = len(queries)
+        excl_q = _per_query_exclude(exclude, B, lambda e: _id_positions(sp, sp._nodes, e, "retriever"))
+        s_kw: Dict[str, Any] = {} if sparse_rows is None else {"rows": sparse_rows}
+        if sparse_filters is not _UNSET:
+            s_kw["filters"] = sparse_filters
+        x_kw: Dict[str, Any] = {} if excl_q is None else {"exclude": excl_q}
+        if self.retrieval_type != 1 and push_filter_dict:
+            sp.filter_dict = self.filter_dict
+        if self.retrieval_type != 2 and push_filters:
+            de.filters = self.filters
+        if self.retrieval_type == 2:
+            return sp.retrieve_batch(queries, filter_dicts=fs, **x_kw, **s_kw)
+        if self.retrieval_type == 1:
+            return de.retrieve_batch(queries, filters=fdn, rows=rows, **x_kw)
+
+        def on_their_own():
+            sparse = sp.retrieve_batch(queries, filter_dicts=fs, **x_kw, **s_kw)
+            dense = de.retrieve_batch(queries, filters=fdn, rows=rows, **x_kw)
+            return [self.reciprocal_rank_fusion([s, d], topk=self.topk) for s, d in zip(sparse, dense)]
+        if not self._fused_possible() or not self._fused_sizes() or rows is not None or sparse_rows is not None:
+            return on_their_own()
+        resolve = lambda e: _id_positions(sp, sp._nodes, e, "retriever")
+        n = len(sp._nodes)
+        fdn_l, d_rows, excl_d = _lift_id_conditions(fdn, None, excl_q, B, n, resolve)
+        sfl, s_rows, excl_s = _lift_id_conditions(None if sparse_filters is _UNSET else sparse_filters, None, excl_q, B, n, resolve)
+        if d_rows is not None or s_rows is not None:
+            return on_their_own()
+        none = [np.zeros(0, np.int64)] * B
+        excl_s, excl_d = excl_s or none, excl_d or none
+        ks, kd = sp._similarity_top_k, de._similarity_top_k
+        if (max(e.size for e in excl_s) + ks > BM25_DEVICE_MAX_K) or (max(e.size for e in excl_d) + kd > DENSE_MAX_K):
+            return on_their_own()
+        spec = _spec_cache()
+        d_sparse = _per_query(fs, B, lambda v: dict(v) if v else None)
+        d_dense = _per_query(fdn_l, B, spec)
+        if sfl is not None:
+            d_sparse = [_both(d, f) for d, f in zip(d_sparse, _per_query(sfl, B, spec))]
+        key_sets = {_spec_keys(fd) for fd in d_sparse + d_dense if _spec_keys(fd)}
+        cstate = sp._corpus_state
+        if len(key_sets) > 1 or any(cstate.too_many_values(ks_) for ks_ in key_sets):
+            return on_their_own()
+        eng = sp.engine
+        sets_s, sets_d = _plan_sets(cstate.plan(d_sparse)), _plan_sets(cstate.plan(d_dense))
+        qi, qt = queries_to_csr([sp._query_ids(q) for q in queries])
+        embs = _unit_f16(np.asarray([de._embed_model.get_query_embedding(q) for q in queries], dtype=np.float32))
+        sids, _, sln = eng.bm25_topk_excl(qi, qt, ks, excl_s, sets=sets_s, device_out=True, slot=sp._slot)
+        dids, _, dln = eng.dense_topk_excl(embs, kd, excl_d, sets=sets_d, device_out=True)
+        fids, fsc, fln = eng.rrf_device(sids, sln, dids, dln, K=60, topk=self.topk)
+        eng.sync()
+        ids, sc, ln = fids.cpu().numpy(), fsc.cpu().numpy(), fln.cpu().numpy()
         nodes = sp._nodes
         return [[NodeWithScore(node=nodes[i], score=float(s)) for i, s in zip(ids[b, :ln[b]], sc[b, :ln[b]])]
                 for b in range(B)]

@@ -39,6 +39,8 @@
  *   erh_bm25_topk_rows   the same where the filter's keep mask is an explicit id set per query (retrievers.py:128-151, 191-210): every listed
  *                        row scored exactly, no scan of the postings
  *   erh_bm25_topk_sets   the same where the keep mask is a set of classes per query (retrievers.py:128-151, 191-210)
+ *   erh_dense_topk_excl  erh_dense_topk_sets minus an id list per query (must_not: [HasIdCondition] beside the filter of retrievers.py:44-47)
+ *   erh_bm25_topk_excl   erh_bm25_topk_sets minus an id list per query (those documents out of the keep mask of retrievers.py:191-210)
  *   erh_rrf              HybridRetriever.reciprocal_rank_fusion (retrievers.py:256-274)
  *   erh_fusion           HybridRetriever.fusion (retrievers.py:239-253)
  *   erh_hybrid_topk      HybridRetriever._aretrieve, retrieval_type == 3 (retrievers.py:276-291)
@@ -337,6 +339,49 @@ int erh_bm25_topk_sets(erh_handle *h, const int32_t *q_indptr, const int32_t *q_
                        const int32_t *set_ptr, const int16_t *set_cls,
                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
 
+/* EXCLUDE LISTS: dense top-k where each query ranks what it may see EXCEPT a list of ids -- a Qdrant filter with
+ * must_not: [HasIdCondition(has_id=[...])] beside the payload conditions the reference's QdrantRetriever hands over unchanged
+ * (src/easyrag/custom/retrievers.py:44-47): a session's chunks already shown, the chunk a HyDE query was built from, the pages in front of
+ * a "search after" page.
+ *   set_ptr / set_cls as for erh_dense_topk_sets; both NULL = every query unfiltered.
+ *   excl_ptr int32[B+1], excl_ids int32[excl_ptr[B]] (host CSR): query b does not see the ids excl_ids[excl_ptr[b] .. excl_ptr[b+1]) -- the
+ *   caller's numbering, strictly ascending per query, in [0, N); excl_ptr[0] = 0, non-decreasing.  An id the query could not see anyway
+ *   (outside its set, never in its top) is legal and changes nothing.  Anything else: ERH_ERR_INVALID, checked on the host before anything
+ *   is enqueued (outputs untouched).
+ *   Depth: kk = k + (the longest exclusion list of the call) must be <= 768, else ERH_ERR_UNSUPPORTED (the message names kk); k < 1 too.
+ * Both modes.  Result for query b: the exact top k of (allowed \ excluded) under the mode's own ranking, canonical order, padded with id -1 /
+ * score 0, out_len[b] = min(k, rows left) -- bit for bit what erh_dense_topk_sets returns for a population without those rows.  How: the
+ * exclusion CSR goes up once, erh_dense_topk_sets' pipeline runs unchanged at depth kk into buffers of the handle, and one kernel
+ * (exclude.hip) removes the excluded ids from each list, in order, and keeps the first k -- at most kk - k entries leave a list, every
+ * survivor keeps its score bits and its place among the survivors.  With every exclusion list empty the result is byte-identical to
+ * erh_dense_topk_sets.
+ * The inner call is checked inside the call (one stream synchronisation), so the contract is erh_dense_topk_rows': no erh_dense_check is
+ * needed, host outputs are final on return, device outputs after erh_sync.  Afterwards erh_dense_diag / erh_dense_exhaustive_count describe
+ * the inner call (its sub-queries at depth kk), and a later erh_dense_check has nothing left to do.  While an earlier device-output
+ * erh_dense_topk / erh_dense_topk_sets / erh_hybrid_topk call still waits for its erh_dense_check the entry returns ERH_ERR_STATE: its inner
+ * call would overwrite that call's work space.
+ * Counters: once in dense_excl_calls and in excl_drop_launches, NOT in dense_calls; the inner pipeline moves the dense_scan_*_launches /
+ * dense_sample_passes / dense_block_* / dense_grouped_launches / dense_exhaustive_queries counters and dense_candidates_last_call /
+ * dense_rescored_rows_last_call like any scan-route call. */
+int erh_dense_topk_excl(erh_handle *h, const void *q, int q_dtype, int q_is_device, int normalize_q, int B, int k,
+                        const int32_t *set_ptr, const int16_t *set_cls, const int32_t *excl_ptr, const int32_t *excl_ids, int mode,
+                        int32_t *out_ids, double *out_scores, int32_t *out_len, int out_is_device, void *stream);
+
+/* The sparse twin: BM25 top-k of what each query may see except its exclusion list (BM25Retriever.get_scores + .filter,
+ * src/easyrag/custom/retrievers.py:128-151, 191-210, with those documents out of the keep mask).  Acts on the slot chosen by erh_bm25_select.
+ *   Queries as for erh_bm25_topk, sets as for erh_bm25_topk_sets (both NULL = unfiltered), exclusion lists as for erh_dense_topk_excl with
+ *   N of the slot.  kk = k + (the longest exclusion list) must be <= 1024, else ERH_ERR_UNSUPPORTED (the message names kk); k < 1 too.
+ * Result for query b: its documents in the set, not excluded, with score > 0, under (score descending, document id ascending), the first
+ * k, scores as the scan wrote them; padded with id -1 / score 0.  erh_bm25_topk_sets' pipeline at depth kk, then the same drop kernel: the
+ * score > 0 cut is a property of the document alone and survives the removal.
+ * Host outputs are final on return, device outputs after erh_sync; no flag words.  The inner pipeline SHARES THE SCAN'S WORK SPACE (as a
+ * routed erh_bm25_topk_rows call does): it must be ordered with the handle's other scan calls like two erh_bm25_topk calls.
+ * Counters: once in bm25_excl_calls and in excl_drop_launches, NOT in bm25_calls or the bm25_sets_* counters; its scans move
+ * bm25_mixed_launches and bm25_redo_segments like any scan. */
+int erh_bm25_topk_excl(erh_handle *h, const int32_t *q_indptr, const int32_t *q_tok, int B, int k, const int32_t *set_ptr,
+                       const int16_t *set_cls, const int32_t *excl_ptr, const int32_t *excl_ids, int32_t *out_ids, double *out_scores,
+                       int32_t *out_len, int out_is_device, void *stream);
+
 /* Dense score vector of one query (host int32[n_tok]) over all N documents: float64[N] on the host
  * (float32 sums widened exactly for ERH_BM25_BM25S).  Mirrors BM25Retriever.get_scores. */
 int erh_bm25_scores(erh_handle *h, const int32_t *q_tok, int n_tok, double *out_scores);
@@ -626,6 +671,8 @@ int erh_dense_exhaustive_count(erh_handle *h, int32_t *count);
  *   bm25_sets_subqueries / bm25_sets_merge_launches    its (query, allowed class) sub-queries, summed over calls / its merge launches (one per call)
  *   dense_rows_scan_calls / bm25_rows_scan_calls       rows calls (either entry) whose long lists took the scan route (each also counts once in *_rows_calls)
  *   dense_rows_scan_subqueries / bm25_rows_scan_subqueries  their (query, cell) sub-queries, summed over calls
+ *   dense_excl_calls / bm25_excl_calls                 erh_dense_topk_excl / erh_bm25_topk_excl calls (counted in no other *_calls counter)
+ *   excl_drop_launches                                 launches of the drop kernel (exclude.hip): one per call of either entry
  *   bm25_mixed_launches                                BM25 scans launched with both bodies (bm25_mixed: a batch with queries longer than bm25_long_tokens)
  *   bm25_redo_segments                                 (query, segment) pairs the fixed-point scan handed to the exact block scan (device counter)
  * Reading a device counter synchronises the device.  Unknown name: ERH_ERR_INVALID. */
