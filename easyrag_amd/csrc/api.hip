@@ -53,6 +53,7 @@ const Option kOptions[] = {
     opt_flag("bm25_dir_range", &H::opt_bm25_dir_range),
     opt_flag("dense_fin_split", &H::opt_dense_fin_split),
     opt_flag("dense_tile384", &H::opt_dense_tile384),
+    opt_flag("dense_mfma16", &H::opt_dense_mfma16),
     opt_i64("dense_tile384_max_mb", &H::opt_tile384_max_mb, INT64_MIN, kOptMax),
     opt_flag("dense_tiled", &H::opt_dense_tiled),                     // building the copy: at the next erh_set_dense
     opt_flag("dense_speculate", &H::opt_dense_speculate),
@@ -481,7 +482,7 @@ int erh_get_stat(erh_handle *h, const char *name, int64_t *value) {
     if (!h || !name || !value) return ERH_ERR_INVALID;
     const erh_handle::Stats &T = h->stats;
     const struct { const char *n; int64_t v; } host[] = {
-        {"dense_calls", T.dense_calls}, {"dense_scan_pp5_launches", T.dense_scan_pp5}, {"dense_scan_pp3_launches", T.dense_scan_pp3},
+        {"dense_calls", T.dense_calls}, {"dense_scan_pp5_launches", T.dense_scan_pp5}, {"dense_scan_mf16_launches", T.dense_scan_mf16}, {"dense_scan_pp3_launches", T.dense_scan_pp3},
         {"dense_scan_gemv_launches", T.dense_scan_gemv}, {"dense_scan_tile_launches", T.dense_scan_tile},
         {"dense_sample_passes", T.dense_sample_passes}, {"dense_tile384_nomem", T.dense_tile384_nomem},
         {"bm25_calls", T.bm25_calls}, {"hybrid_calls", T.hybrid_calls}, {"dense_block_groups", T.dense_block_groups},

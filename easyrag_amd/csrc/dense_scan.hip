@@ -25,6 +25,7 @@
 //   1: 128 x 256, BK 32, 4 waves, A ring 4 / B ring 3,  80 KiB LDS  -> two independent workgroups per CU,
 //      whose barrier / issue bubbles overlap each other's MFMA phases
 #include <algorithm>
+#include <type_traits>
 #include "common.h"
 #include "kernels.h"
 
@@ -1150,6 +1151,15 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp3_kernel(
 //     with 384 rows for the chunk matrix -- built once per erh_set_dense, on first use -- and 256 rows for the query block
 //     of the call): every DMA instruction moves 1 KiB of consecutive bytes, addresses are a wave-uniform pointer + lane * 16;
 //   - a record carries nine row bits (tile index: 17 bits).
+// Two bodies, one geometry (template parameter MF, option dense_mfma16): MF = 0 issues v_mfma_f32_32x32x16_f16 as described above;
+// MF = 1 issues v_mfma_f32_16x16x32_f16 over 12 x 4 accumulator blocks of 16 x 16 (the same 192 rows x 64 queries per wave, the same
+// 192 accumulator VGPRs) -- same cycles per FLOP, but the chip, which holds this loop's clock down under load, holds it higher on this
+// shape (scripts/ubench/scan_tile384.hip, profiles/mfma16_ubench_scan_tile384.log; DESIGN K1).  Rings, LDS-DMA, barriers, stage
+// images, launch geometry, record word and flush are common to both; what differs is the fragment address, the matrix segment
+// (ERH_PP5_STAGE16) and the accumulator -> (row, query) formula of the epilogue (ERH_PP5_TESTS16).  The fp32 scores only prune
+// (select.hip lowers every threshold by margin_of(), which bounds the fp32 error of any summation order), so the results are
+// bit-identical whichever body ran.
+typedef float f32x4 __attribute__((ext_vector_type(4)));   // accumulator block of v_mfma_f32_16x16x32_f16
 namespace pp5 {
 constexpr int BM = 384, MT = 6, GROWS = 192, ROW_BITS = 9, AST = 4, BST = 3;
 constexpr int A_BYTES = BM * pp::RB;
@@ -1165,6 +1175,7 @@ static_assert(CAPW <= 192 && TAU_OFF + 64 * 4 == pp::REC_BYTES && pp::CAPW >= CA
 static_assert(B_BASE + BST * pp::B_BYTES == pp::REC_BASE, "records and flush flags sit where the 256-row kernels have them");
 }  // namespace pp5
 
+template <int MF>
 __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
     const _Float16 *__restrict__ Xt, int64_t N, int d, int64_t c0, int64_t c1,
     const _Float16 *__restrict__ Qt, int Bpad, int B,
@@ -1223,6 +1234,18 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
                      "v_lshlrev_b32 %0, 6, %0\n\tv_lshl_or_b32 %0, %1, 4, %0"                                       \
                      : "=&v"(F), "=&v"(t_), "=&v"(u_));                                               \
     } while (0)
+// MF = 1: row (lane & 15) of a 16-row block, slot (lane >> 4) ^ ((lane >> 2) & 3) on the same stage images.  Sixteen consecutive lanes
+// cover 16 distinct (row & 3, physical slot) pairs, but the hardware does not serve a ds_read_b128 in those groups: the counters show
+// the read two-way conflicted (SQ_LDS_BANK_CONFLICT 0.49 of SQ_LDS_IDX_ACTIVE against 0 for MF = 0, profiles/mfma16_pmc_dense_b1024.txt).
+// The body wins regardless; a swizzle that serves both bodies conflict-free would need other stage images.
+#define ERH_PP5_FADR16(F)                                                                             \
+    do {                                                                                              \
+        int t_, u_;                                                                                   \
+        asm volatile("v_mbcnt_lo_u32_b32 %1, -1, 0\n\tv_mbcnt_hi_u32_b32 %1, -1, %1\n\tv_and_b32 %0, 15, %1\n\t"   \
+                     "v_lshrrev_b32 %1, 4, %1\n\tv_bfe_u32 %2, %0, 2, 2\n\tv_xor_b32 %1, %1, %2\n\t"                \
+                     "v_lshlrev_b32 %0, 6, %0\n\tv_lshl_or_b32 %0, %1, 4, %0"                                       \
+                     : "=&v"(F), "=&v"(t_), "=&v"(u_));                                               \
+    } while (0)
     const int a_wave = __builtin_amdgcn_readfirstlane(grp * pp5::GROWS * pp::RB);
     const int b_wave = __builtin_amdgcn_readfirstlane(pp5::B_BASE + wave_n * 64 * pp::RB);
     char *const rec = lds + pp::REC_BASE + wave * pp::REC_BYTES;
@@ -1233,7 +1256,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
     int a_left = total, b_left = total;
     int fa_off = 0, fb_off = 0;                                        // ring offsets of the stage whose FIRST half is read next
     int cur_a = 0, cur_b = 0;                                          // ... of the stage whose SECOND half is read next
-    half8 fa[pp5::MT], fb[2];
+    half8 fa[MF ? 4 : pp5::MT], fb[MF ? 4 : 2];                        // (MF = 1: a rolling ring of four chunk-side blocks + the stage's query side)
     // LDS-DMA by inline assembly in the scalar-base form: wave-uniform 64-bit source in SGPRs + this lane's 32-bit byte offset,
     // destination = M0 (wave-uniform LDS byte address; lane i lands at + 16 i).  Through the builtin the compiler keeps a 64-bit
     // per-lane pointer per operand, which this kernel has no registers for.
@@ -1324,6 +1347,67 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
         fb_off += pp::B_BYTES;                                                                        \
         if (fb_off == kBBytes) fb_off = 0;                                                            \
     } while (0)
+// MF = 1 (v_mfma_f32_16x16x32_f16: 12 x 4 accumulator blocks of 16 x 16, a K step is the whole stage).  The 32 fragment registers
+// hold the stage's four query-side fragments and a four-deep rolling ring of chunk-side fragments: chunk block a meets the four
+// query blocks, then its ring slot takes block a + 4 (of the next stage from block 8 on) -- every operand is read from LDS once
+// per stage, as in the MF = 0 body.  The first two and the last two blocks of a stage go query-block-outer; the query-side
+// fragments are replaced behind the last pair that reads them, >= 6 MFMAs before the next stage's first pair does.  The re-loads
+// return in order, so each group waits with lgkmcnt(n) for its own operands only (n = what was issued behind them); the order
+// of a stage's re-loads is  4 5 | 6 7 8 9 10 11 0' 1' | q0' q1' q2' q3' 2' 3'  (' = stage g + 1).
+#define ERH_PP5_LGKM(N_) do { asm volatile("s_waitcnt lgkmcnt(" #N_ ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define ERH_PP5_MF16(A_, N_, S_, Z_)                                                                  \
+    acc[A_][N_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[S_], fb[N_], (Z_) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[A_][N_], 0, 0, 0)
+#define ERH_PP5_STAGE16(Z_)                                                                           \
+    do {                                                                                              \
+        { int pa_, f_;                                                                                \
+          ERH_PP5_FADR16(f_);                                                                         \
+          asm volatile("v_add_u32 %0, %2, %1" : "=&v"(pa_) : "v"(f_), "s"(a_wave + cur_a));           \
+          ERH_PP5_LGKM(5); ERH_PP5_MF16(0, 0, 0, Z_); ERH_PP5_MF16(1, 0, 1, Z_); __builtin_amdgcn_sched_barrier(0); \
+          ERH_PP5_LGKM(4); ERH_PP5_MF16(0, 1, 0, Z_); ERH_PP5_MF16(1, 1, 1, Z_); __builtin_amdgcn_sched_barrier(0); \
+          ERH_PP5_LGKM(3); ERH_PP5_MF16(0, 2, 0, Z_); ERH_PP5_MF16(1, 2, 1, Z_); __builtin_amdgcn_sched_barrier(0); \
+          ERH_PP5_LGKM(2); ERH_PP5_MF16(0, 3, 0, Z_); ERH_PP5_MF16(1, 3, 1, Z_); __builtin_amdgcn_sched_barrier(0); \
+          ERH_PP5_LD(fa[0], pa_, 4 * 16 * pp::RB);                                                    \
+          ERH_PP5_LD(fa[1], pa_, 5 * 16 * pp::RB);                                                    \
+          __builtin_amdgcn_sched_barrier(0);                                                          \
+          _Pragma("unroll") for (int a = 2; a < 8; ++a) {                                             \
+              ERH_PP5_LGKM(3);                                                                        \
+              _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) ERH_PP5_MF16(a, nt, a & 3, Z_);        \
+              __builtin_amdgcn_sched_barrier(0);                                                      \
+              ERH_PP5_LD(fa[a & 3], pa_, (a + 4) * 16 * pp::RB);                                      \
+              __builtin_amdgcn_sched_barrier(0);                                                      \
+          } }                                                                                         \
+        { int pa_, pb_, f_;                                                                           \
+          ERH_PP5_FADR16(f_);                                                                         \
+          asm volatile("v_add_u32 %0, %3, %2\n\tv_add_u32 %1, %4, %2"                                 \
+                       : "=&v"(pa_), "=&v"(pb_) : "v"(f_), "s"(a_wave + fa_off), "s"(b_wave + fb_off)); \
+          _Pragma("unroll") for (int a = 8; a < 10; ++a) {                                            \
+              ERH_PP5_LGKM(3);                                                                        \
+              _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) ERH_PP5_MF16(a, nt, a & 3, Z_);        \
+              __builtin_amdgcn_sched_barrier(0);                                                      \
+              ERH_PP5_LD(fa[a & 3], pa_, (a - 8) * 16 * pp::RB);                                      \
+              __builtin_amdgcn_sched_barrier(0);                                                      \
+          }                                                                                           \
+          ERH_PP5_LGKM(2);                                                                            \
+          _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                                          \
+              ERH_PP5_MF16(10, nt, 2, Z_); ERH_PP5_MF16(11, nt, 3, Z_);                               \
+              __builtin_amdgcn_sched_barrier(0);                                                      \
+              ERH_PP5_LD(fb[nt], pb_, nt * 16 * pp::RB);                                              \
+              __builtin_amdgcn_sched_barrier(0);                                                      \
+          }                                                                                           \
+          ERH_PP5_LD(fa[2], pa_, 2 * 16 * pp::RB);                                                    \
+          ERH_PP5_LD(fa[3], pa_, 3 * 16 * pp::RB);                                                    \
+          __builtin_amdgcn_sched_barrier(0); }                                                        \
+    } while (0)
+#define ERH_PP5_COMPUTE16(FIRST)                                                                      \
+    do {                                                                                              \
+        if (FIRST) ERH_PP5_STAGE16(true); else ERH_PP5_STAGE16(false);                                \
+        cur_a = __builtin_amdgcn_readfirstlane(fa_off);                                               \
+        cur_b = __builtin_amdgcn_readfirstlane(fb_off);                                               \
+        fa_off += pp5::A_BYTES;                                                                       \
+        if (fa_off == kABytes) fa_off = 0;                                                            \
+        fb_off += pp::B_BYTES;                                                                        \
+        if (fb_off == kBBytes) fb_off = 0;                                                            \
+    } while (0)
 // after M_g (query stage g+2, then chunk stage g+3 issued): everything but the three chunk-side instructions has landed, i.e.
 // stage g+2; the fragment reads of this wave's last matrix segment have retired (ring slots may be overwritten after the barrier)
 #define ERH_PP5_WAIT(G)                                                                               \
@@ -1335,6 +1419,44 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
 // come from the wave's LDS slots (pp5::TAU_OFF), not from registers held -- i.e. spilled -- across the main loop: -0.7 % scan time,
 // no scratch access inside the tile loop.  (Measured and NOT kept: pp3's mask-first group tests in two halves of three block rows,
 // +-0 here; with no epilogue at all the scan class is 5.6 % faster -- profiles/r05e_ab_pp5_epilogue.log.)
+// MF = 1: a lane owns query nt * 16 + (lane & 15) and rows mt * 16 + 4 * (lane >> 4) + r of its group's 192; the same 48 group tests
+// per lane, the same record word (ERH_PP_EPI_QUAD_C with the 16 x 16 row formula)
+#define ERH_PP5_EPI_QUAD16(MT, NT)                                                                    \
+    do {                                                                                              \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                               \
+            const float sc_ = acc[MT][NT][r];                                                         \
+            const bool hit_ = sc_ >= t_;                                                              \
+            const unsigned long long m_ = __builtin_amdgcn_ballot_w64(hit_);                          \
+            if (m_) {                                                                                 \
+                const int pos_ = cnt_ - shift_ +                                                      \
+                    (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m_ >> 32),                              \
+                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)m_, 0u));      \
+                if (hit_ && (unsigned)pos_ < (unsigned)pp5::CAPW) {                                   \
+                    *reinterpret_cast<float *>(rec + pos_ * 4) = sc_;                                 \
+                    *reinterpret_cast<uint32_t *>(rec + 1024 + pos_ * 4) = pk_l_ + ((uint32_t)((MT) * 16 + r) << 6); \
+                }                                                                                     \
+                cnt_ += __builtin_popcountll(m_);                                                     \
+            }                                                                                         \
+            __builtin_amdgcn_sched_barrier(0);   /* keeps one ballot mask live at a time */           \
+        }                                                                                             \
+    } while (0)
+#define ERH_PP5_TESTS16()                                                                             \
+    do {                                                                                              \
+        const uint32_t ta_ = lds0 + (uint32_t)(pp::REC_BASE + pp5::TAU_OFF) + (uint32_t)wave * (uint32_t)pp::REC_BYTES + \
+                             (uint32_t)(lane & 15) * 4u;                                              \
+        _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                                            \
+            float t_;                                                                                 \
+            asm volatile("ds_read_b32 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(t_) : "v"(ta_), "n"(nt * 64) : "memory"); \
+            uint32_t pk_l_ = (uint32_t)(nt * 16 + (lane & 15)) | ((uint32_t)(grp * pp5::GROWS + 4 * (lane >> 4)) << 6) | \
+                             ((uint32_t)i << (6 + pp5::ROW_BITS));                                    \
+            asm volatile("" : "+v"(pk_l_));                                                           \
+            _Pragma("unroll") for (int mt = 0; mt < 12; ++mt) {                                       \
+                const bool any_ = erh_max4(acc[mt][nt][0], acc[mt][nt][1], acc[mt][nt][2], acc[mt][nt][3]) >= t_; \
+                if (__builtin_amdgcn_ballot_w64(any_)) ERH_PP5_EPI_QUAD16(mt, nt);                    \
+                __builtin_amdgcn_sched_barrier(0);                                                    \
+            }                                                                                         \
+        }                                                                                             \
+    } while (0)
 #define ERH_PP5_EPILOGUE()                                                                            \
     do {                                                                                              \
         int lane, l31, hh;      /* re-derived here (opaque to the compiler): not held in registers across the main loop */ \
@@ -1345,6 +1467,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
         const int fill0_ = fill;                                                                      \
         for (int shift_ = 0;; shift_ += pp5::CAPW) {                                                   \
             int cnt_ = fill0_;                                                                        \
+            if constexpr (MF == 0) {                                                                  \
             float tt_[2];                                                                             \
             {                                                                                         \
                 const uint32_t ta_ = lds0 + (uint32_t)(pp::REC_BASE + pp5::TAU_OFF) + (uint32_t)wave * (uint32_t)pp::REC_BYTES + \
@@ -1365,6 +1488,9 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
                         __builtin_amdgcn_sched_barrier(0);                                            \
                     }                                                                                 \
                 }                                                                                     \
+            }                                                                                         \
+            } else {                                                                                  \
+                ERH_PP5_TESTS16();                                                                    \
             }                                                                                         \
             const int avail_ = cnt_ - shift_;                                                         \
             const bool over_ = avail_ > pp5::CAPW;                                                     \
@@ -1411,27 +1537,35 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
     ERH_PP5_ISSUE_A(); ERH_PP5_ISSUE_B(); ERH_PP5_ISSUE_A(); ERH_PP5_ISSUE_B(); ERH_PP5_ISSUE_A();
     if (total >= 4) asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ERH_PP_BARRIER();
-    {
+    if constexpr (MF == 0) {
         int f_adr0;
         ERH_PP5_FADR(f_adr0);
 #pragma unroll
         for (int mt = 0; mt < pp5::MT; ++mt) fa[mt] = *reinterpret_cast<const half8 *>(lds + f_adr0 + a_wave + mt * 32 * pp::RB);
         fb[0] = *reinterpret_cast<const half8 *>(lds + f_adr0 + b_wave);
         fb[1] = *reinterpret_cast<const half8 *>(lds + f_adr0 + b_wave + 32 * pp::RB);
+    } else {                                                           // chunk blocks 0 .. 3 and the four query blocks of stage 0
+        int f_adr0;
+        ERH_PP5_FADR16(f_adr0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            fa[j] = *reinterpret_cast<const half8 *>(lds + f_adr0 + a_wave + j * 16 * pp::RB);
+            fb[j] = *reinterpret_cast<const half8 *>(lds + f_adr0 + b_wave + j * 16 * pp::RB);
+        }
     }
-    fa_off = pp5::A_BYTES;                                             // (stage 0's first half is in registers, its second half is cur_* = 0)
+    fa_off = pp5::A_BYTES;                                             // (stage 0's first half is in registers, its second half is cur_* = 0; MF = 1: its first re-loads)
     fb_off = pp::B_BYTES;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     ERH_PP_BARRIER();
 
-    f32x16 acc[pp5::MT][2];
+    std::conditional_t<MF == 0, f32x16, f32x4> acc[MF ? 12 : pp5::MT][MF ? 4 : 2];
     int fill = 0;                                                      // records buffered in this wave's area
     int flush_now = 0;                                                 // workgroup-uniform, decided one tile ahead
     int g = 0;
     if (grp == 0) {
         for (int i = 0; i < n_tiles; ++i) {
             for (int kt = 0; kt < nk; ++kt, ++g) {
-                ERH_PP5_COMPUTE(kt == 0);                              // C(g)
+                if constexpr (MF == 0) ERH_PP5_COMPUTE(kt == 0); else ERH_PP5_COMPUTE16(kt == 0);   // C(g)
                 ERH_PP_BARRIER();                                      // |A|
                 ERH_PP5_ISSUE_B();                                     // M_g: the query side first (it is waited for)
                 ERH_PP5_ISSUE_A();
@@ -1450,7 +1584,7 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
                 ERH_PP5_ISSUE_A();
                 __builtin_amdgcn_sched_barrier(0);
                 ERH_PP_BARRIER();                                      // |A|
-                ERH_PP5_COMPUTE(kt == 0);                              // C(g)
+                if constexpr (MF == 0) ERH_PP5_COMPUTE(kt == 0); else ERH_PP5_COMPUTE16(kt == 0);   // C(g)
                 ERH_PP5_WAIT(g);
                 ERH_PP_BARRIER();                                      // |B|
             }
@@ -1469,6 +1603,13 @@ __global__ __launch_bounds__(pp::NT) void dense_scan_pp5_kernel(
 #undef ERH_PP5_COMPUTE
 #undef ERH_PP5_WAIT
 #undef ERH_PP5_EPILOGUE
+#undef ERH_PP5_FADR16
+#undef ERH_PP5_LGKM
+#undef ERH_PP5_MF16
+#undef ERH_PP5_STAGE16
+#undef ERH_PP5_COMPUTE16
+#undef ERH_PP5_EPI_QUAD16
+#undef ERH_PP5_TESTS16
 }
 
 // tiled copy with `rows` rows per tile (384: the chunk matrix for dense_scan_pp5_kernel): per tile and 32-half stage one block
@@ -1758,7 +1899,8 @@ hipError_t dense_scan_init() {
 #define ERH_SET_PP3(A, V) ERH_SET_LDS((dense_scan_pp3_kernel<A, V>))
     ERH_PP3_VARIANTS(ERH_SET_PP3)
 #undef ERH_SET_PP3
-    ERH_SET_LDS(dense_scan_pp5_kernel)
+    ERH_SET_LDS(dense_scan_pp5_kernel<0>)
+    ERH_SET_LDS(dense_scan_pp5_kernel<1>)
 #ifdef ERH_MEASURE
     ERH_SET_LDS(dense_scan_pp_kernel<0>)
 #define ERH_SET_PP2(A, V) ERH_SET_LDS((dense_scan_pp2_kernel<A, V>))
@@ -1855,8 +1997,9 @@ hipError_t launch_dense_tile_rows_n(const _Float16 *X, int64_t N, int d, int row
 }
 
 // The 384 x 256 ping-pong scan (dense_scan_pp5_kernel): a.X = launch_dense_tile_rows_n(X, N, d, 384), a.Q = launch_dense_tile_rows of the
-// query block; c0 must be a multiple of 384, Bpad >= 512.  hipErrorInvalidValue when the shape does not qualify.
-hipError_t launch_dense_scan_pp5(const ErhScanArgs &a, int n_cus, int rot_stages, hipStream_t st) {
+// query block; c0 must be a multiple of 384, Bpad >= 512.  hipErrorInvalidValue when the shape does not qualify.  mf16: the body on
+// v_mfma_f32_16x16x32_f16 (same geometry, same records).
+hipError_t launch_dense_scan_pp5(const ErhScanArgs &a, int n_cus, int rot_stages, bool mf16, hipStream_t st) {
     if (a.c1 <= a.c0) return hipSuccess;
     if (a.d % 64 != 0 || a.d / pp::BK < 8 || a.c0 % pp5::BM != 0 || a.Bpad % pp::BN != 0 || a.Bpad < 2 * pp::BN) return hipErrorInvalidValue;
     const int n_qt = a.Bpad / pp::BN;
@@ -1864,7 +2007,8 @@ hipError_t launch_dense_scan_pp5(const ErhScanArgs &a, int n_cus, int rot_stages
     if (grid_n <= 0) return hipErrorInvalidValue;
     const int64_t n_ct = (a.c1 - a.c0 + pp5::BM - 1) / pp5::BM;
     if (n_ct / (grid_n / n_qt) + 1 >= (1ll << pp5::TILE_BITS)) return hipErrorInvalidValue;   // tile index must fit the record
-    hipLaunchKernelGGL(dense_scan_pp5_kernel, dim3((unsigned)grid_n), dim3(pp::NT), pp::LDS_BYTES, st, ERH_SCAN_ARGS(a), rot_stages);
+    if (mf16) hipLaunchKernelGGL(dense_scan_pp5_kernel<1>, dim3((unsigned)grid_n), dim3(pp::NT), pp::LDS_BYTES, st, ERH_SCAN_ARGS(a), rot_stages);
+    else hipLaunchKernelGGL(dense_scan_pp5_kernel<0>, dim3((unsigned)grid_n), dim3(pp::NT), pp::LDS_BYTES, st, ERH_SCAN_ARGS(a), rot_stages);
     return hipGetLastError();
 }
 

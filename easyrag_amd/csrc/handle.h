@@ -301,7 +301,7 @@ struct erh_handle {
     // dstats[2] queries of fused calls whose final kernel re-scored less than the margin set (hybrid_lazy_queries)
     DevBuf dstats;
     struct Stats {
-        int64_t dense_calls = 0, dense_scan_pp5 = 0, dense_scan_pp3 = 0, dense_scan_gemv = 0, dense_scan_tile = 0,
+        int64_t dense_calls = 0, dense_scan_pp5 = 0, dense_scan_mf16 = 0, dense_scan_pp3 = 0, dense_scan_gemv = 0, dense_scan_tile = 0,
                 dense_sample_passes = 0, dense_tile384_nomem = 0, bm25_calls = 0, hybrid_calls = 0, dense_block_groups = 0,
                 dense_grouped_launches = 0, bm25_mixed_launches = 0, dense_rows_calls = 0, dense_rows_short = 0, dense_rows_long = 0,
                 dense_group_reruns = 0, bm25_rows_calls = 0, bm25_rows_short = 0, bm25_rows_long = 0,
@@ -344,6 +344,7 @@ struct erh_handle {
     int opt_n0_auto = 0;                   // seed prefix snapped down to a whole number of scan rounds (less seed work, more candidates: a wash at 1M chunks)
     int opt_dense_sync = 0;                // the query-tile workgroups of a stream meet at a counter every four tiles (measured: no gain)
     int opt_dense_selfseed = 1;            // the ping-pong scan draws its own threshold sample (sample pass + cell maxima) instead of store kernel + S0 + seed select
+    int opt_dense_mfma16 = 1;              // the 384 x 256 scan issues v_mfma_f32_16x16x32_f16 (dense_scan_pp5_kernel<1>); same results, see DESIGN K1
     int opt_dense_tile384 = 1;             // batches padded to >= 512 queries scan on a 384 x 256 tile over tiled operands (+ N * d * 2 bytes on first use)
     int opt_dense_tiled = 0;               // keep a tiled, pre-swizzled copy of the chunk matrix for the ping-pong scan (+ N * d * 2 bytes; no measurable gain: off)
     int opt_dense_speculate = 1;           // speculative (verified) first threshold + a single scan stage; 0: guaranteed bounds, refined in stages

@@ -103,7 +103,7 @@ hipError_t launch_dense_scan_pp(const ErhScanArgs &a, int n_cus, int pabl, unsig
 // the query block; c0 a multiple of 384.  hipErrorInvalidValue when the shape does not qualify (the caller falls through).
 int dense_scan_pp5_rows();
 hipError_t launch_dense_tile_rows_n(const _Float16 *X, int64_t N, int d, int rows, void *Xt, hipStream_t st);
-hipError_t launch_dense_scan_pp5(const ErhScanArgs &a, int n_cus, int rot_stages, hipStream_t st);
+hipError_t launch_dense_scan_pp5(const ErhScanArgs &a, int n_cus, int rot_stages, bool mf16, hipStream_t st);
 // tiled copy of the chunk matrix for the ping-pong scan: ceil(N / 256) * 256 * d halves (see dense_tile_rows_kernel)
 hipError_t launch_dense_tile_rows(const _Float16 *X, int64_t N, int d, void *Xt, hipStream_t st);
 constexpr int kDensePadRows = 384;   // zero rows erh_set_dense keeps behind the matrix (tiles past N read them: up to 383 for the 384-row tile)

@@ -47,8 +47,9 @@ static hipError_t scan_append(erh_handle *h, const erh::ErhScanArgs &a, hipStrea
         // 384 x 256 tile over the tiled copies (the caller checked the options and built the copies)
         t.X = h->Xt384.as<_Float16>(); t.Q = h->Qt.as<_Float16>();
         hipError_t e = erh::launch_dense_scan_pp5(t, h->n_cus,
-                                                  h->opt_dense_rot >= 0 ? h->opt_dense_rot : 0 /* the workgroups of a stream on the same stage: measured best here (profiles/r04w_kbench_tile384.log) */, st);
-        if (e != hipErrorInvalidValue) { h->stats.dense_scan_pp5 += (c1 > c0); return e; }
+                                                  h->opt_dense_rot >= 0 ? h->opt_dense_rot : 0 /* the workgroups of a stream on the same stage: measured best here (profiles/r04w_kbench_tile384.log) */,
+                                                  h->opt_dense_mfma16 != 0, st);
+        if (e != hipErrorInvalidValue) { h->stats.dense_scan_pp5 += (c1 > c0); h->stats.dense_scan_mf16 += (c1 > c0 && h->opt_dense_mfma16); return e; }
         (void)hipGetLastError();
     }
 #ifdef ERH_MEASURE

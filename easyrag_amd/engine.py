@@ -725,7 +725,7 @@ class RetrievalEngine:
         self._check(self._lib.erh_dense_exhaustive_count(self._h, C.byref(x)))
         return {"max_abs_err": e.value, "margin": m.value, "uncertified": u.value, "exhaustive": x.value}
 
-    STAT_NAMES = ("dense_calls", "bm25_calls", "hybrid_calls", "dense_scan_pp5_launches", "dense_scan_pp3_launches",
+    STAT_NAMES = ("dense_calls", "bm25_calls", "hybrid_calls", "dense_scan_pp5_launches", "dense_scan_mf16_launches", "dense_scan_pp3_launches",
                   "dense_scan_gemv_launches", "dense_scan_tile_launches", "dense_sample_passes", "dense_tile384_nomem",
                   "dense_exhaustive_queries", "bm25_redo_segments", "dense_block_groups", "dense_grouped_launches", "bm25_mixed_launches",
                   "dense_rows_calls", "dense_rows_short_launches", "dense_rows_long_launches", "dense_group_reruns",

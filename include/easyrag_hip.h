@@ -496,6 +496,9 @@ int erh_reset_kernel_time(erh_handle *h);
  *   dense_tile384 (1)     batches padded to >= 512 queries: scan on a 384 x 256 tile over tiled copies of both operands
  *                         (dense_scan_pp5_kernel; the 384-row copy of the chunk matrix, + N * d * 2 bytes, is built on first use);
  *                         0 = the 256 x 256 tile for every batch size
+ *   dense_mfma16 (1)      the 384 x 256 scan issues its matrix instructions as 16x16x32 instead of 32x32x16 (same tile, same launch
+ *                         geometry, same records: dense_scan_pp5_kernel<1>); the fp32 scan scores only prune, so results are
+ *                         bit-identical either way
  *   dense_tile384_max_mb (-1)  test hook: a 384-row copy larger than this many MiB is refused as if its allocation had failed
  *                         (the 256 x 256 scan then serves every batch; -1 = no limit); the per-dir block copies (dense_dir_blocks)
  *                         obey the same bound and fall back the same way (to the filter column)
@@ -644,6 +647,7 @@ int erh_dense_exhaustive_count(erh_handle *h, int32_t *count);
  * the kernel under test ran, bench.py reports that no query of the timed steps left the pruned pipeline).  Counters:
  *   dense_calls / bm25_calls / hybrid_calls           entry-point calls
  *   dense_scan_pp5_launches                            dense scan launches on the 384 x 256 tile (dense_scan_pp5_kernel)
+ *   dense_scan_mf16_launches                           ... of which on the 16x16x32 body (dense_mfma16)
  *   dense_scan_pp3_launches                            ... on the 256 x 256 ping-pong tile (main scans; sample passes are counted apart)
  *   dense_scan_gemv_launches / dense_scan_tile_launches  ... on the skinny-GEMM stream / the per-tile fallback kernels
  *   dense_sample_passes                                threshold samples drawn by the scan kernel itself (dense_selfseed)

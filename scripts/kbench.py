@@ -280,6 +280,19 @@ def main():
             res[f"dense B=1024 k=288 tile384=1 rot={rot} #{len(res)}"] = r
         eng.set_option("dense_rot", 0)
         del x
+    if what == "mfma16":                                     # 16x16x32 body of the 384 x 256 scan (dense_mfma16) against the 32x32x16 one
+        x = synth.dense_corpus_torch(n, d, seed=2, device=dev)
+        eng.set_dense(x)
+        was = eng.get_option("dense_mfma16")
+        for B, k in ((1024, 288), (512, 100), (768, 100)):
+            q = synth.dense_queries_torch(x, B, seed=7)
+            for m in (1, 0, 1, 0):
+                eng.set_option("dense_mfma16", m)
+                r = timed(eng, lambda: eng.dense_topk(q, k, device_out=True), 20)
+                r["sum"] = round(sum(r.values()), 4)
+                res[f"dense B={B} k={k} mfma16={m} #{len(res)}"] = r
+        eng.set_option("dense_mfma16", was)
+        del x
     if what == "p3":                                         # strict-alternation ping-pong (dense_pp=3) vs the lean one (2)
         x = synth.dense_corpus_torch(n, d, seed=2, device=dev)
         eng.set_dense(x)

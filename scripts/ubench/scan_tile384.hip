@@ -212,9 +212,164 @@ __global__ __launch_bounds__(512) void k(const char *__restrict__ X, int64_t n_t
     if (threadIdx.x == 0 && blockIdx.x == 0) reinterpret_cast<long long *>(sink)[1] = clock64() - t_start;
 }
 
-template <int ROWS, int SHARE, int NA, int NB>
+
+// ---- the same mainloop on v_mfma_f32_16x16x32_f16 (rings, DMA, barriers and waits are k's, through its macros) ----
+// A wave's tile is (ROWS / 32) x 4 accumulator blocks of 16 x 16 (the same ROWS / 2 rows x 64 queries, the same accumulator
+// registers).  A K step is the whole 32-half stage, so the 32 fragment registers of the 384-row tile cannot be "half a stage" by
+// K; two schedules that fit them:
+//   SCHED 0: the stage's four query-side fragments held (16 VGPRs) + a four-deep rolling ring of chunk-side fragments (16): each
+//            chunk block meets the four query blocks, then its ring slot takes the block four ahead (of the next stage at the
+//            end).  The first two and the last two blocks of a stage go query-block-outer, so that the query-side fragments are
+//            replaced (behind the last pair) >= 6 MFMAs before the next stage reads them.  Every operand is read once per stage.
+//   SCHED 1: quarters of MB / 2 chunk blocks x 2 query blocks (24 + 8 VGPRs at 384 rows) in snake order (A0,B0) (A0,B1) (A1,B1)
+//            (A1,B0), query-block-outer inside a quarter; query blocks 0 and 1 are read twice per stage (+2 of 16 ds_read_b128).
+// Fragment of lane l: row l & 15 of its 16-row block, logical 16-byte slot l >> 4, physical slot ^ ((row >> 2) & 3) as in the
+// stage images (sixteen consecutive lanes cover 16 distinct (row & 3, slot) pairs; the product kernel's counters nevertheless show this
+// read two-way bank-conflicted -- profiles/mfma16_pmc_dense_b1024.txt).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// (lane * 16 re-computed at each DMA issue instead of held: the 384-row variants have no register to spare -- as the scan does)
+static __device__ __forceinline__ int lane_off16() {
+    int v;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0\n\tv_lshlrev_b32 %0, 4, %0" : "=v"(v));
+    return v;
+}
+#define lane_off lane_off16()
+template <int ROWS, int SHARE, int NA, int NB, int SCHED>
+__global__ __launch_bounds__(512) void k16(const char *__restrict__ X, int64_t n_tiles, const char *__restrict__ Q,
+                                           float *__restrict__ sink) {
+    constexpr int MB = ROWS / 32;                                  // 16-row accumulator blocks per wave
+    constexpr int HB = MB / 2;
+    constexpr int kAStage = ROWS * 64;
+    constexpr int kA = NA * kAStage, kB = NB * 16384;
+    constexpr int kAIns = kAStage / 8192;
+    constexpr bool B_FIRST = NB == 3;
+    constexpr int kInFlight = B_FIRST ? kAIns : kAIns + 2;
+    constexpr int kPrologueWait = (NA - 3) * kAIns + (NB - 3) * 2;
+    static_assert(NA >= 4 && NB >= 3, "ring depths");
+    constexpr int kTileBytes = ROWS * 1024 * 2;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int grp = wave >> 2, wave_n = wave & 3;
+    const int xcd = blockIdx.x & 7, jx = blockIdx.x >> 3;
+    const int qt = jx % SHARE;
+    const int stream = (jx / SHARE) * 8 + xcd;
+    const int n_streams = gridDim.x / SHARE;
+    Q += (int64_t)qt * kQTileBytes;
+    const int tiles_mine = (int)((n_tiles - stream + n_streams - 1) / n_streams);
+    const int total = tiles_mine * kStages;
+    const long long t_start = clock64();
+
+    f32x4 acc[MB][4];
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[mb][nt][r] = 0.f;
+    constexpr int NFA = SCHED == 0 ? 4 : HB, NFB = SCHED == 0 ? 4 : 2;
+    half8 fa[NFA], fb[NFB];
+    const int l15 = lane & 15;
+    const int slot = (lane >> 4) ^ ((lane >> 2) & 3);
+    const int a_adr0 = (grp * (ROWS / 2) + l15) * 64 + (slot << 4), b_adr0 = kA + (wave_n * 64 + l15) * 64 + (slot << 4);
+
+    const char *xa = X + (int64_t)stream * kTileBytes + wave * 1024;
+    const char *qb = Q + wave * 1024;
+    int s_a = 0, s_b = 0, a_dst = 0, b_dst = 0;
+    char *const my_dst = lds + wave * 1024;
+    const int64_t a_tile_jump = (int64_t)n_streams * kTileBytes - (int64_t)kTileBytes;
+    int fa_off = 0, fb_off = 0;
+    int cur_a = 0, cur_b = 0;
+#define LD16(P_) (*reinterpret_cast<const half8 *>(P_))
+#define MF16(A_, N_, FA_, FB_) acc[A_][N_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(FA_, FB_, acc[A_][N_], 0, 0, 0)
+#define SB() __builtin_amdgcn_sched_barrier(0)
+    // matrix segment of stage g: pa_ / pb_ its images, pan_ / pbn_ those of stage g + 1 (what k's second half re-loads from)
+#define COMPUTE16()                                                                                    \
+    do {                                                                                               \
+        const char *pa_ = lds + a_adr0 + cur_a, *pb_ = lds + b_adr0 + cur_b;                           \
+        const char *pan_ = lds + a_adr0 + fa_off, *pbn_ = lds + b_adr0 + fb_off;                       \
+        if (SCHED == 0) {                                                                              \
+            _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) { MF16(0, nt, fa[0], fb[nt]); MF16(1, nt, fa[1], fb[nt]); } \
+            SB(); fa[0] = LD16(pa_ + 4 * 1024); fa[1] = LD16(pa_ + 5 * 1024); SB();                          \
+            _Pragma("unroll") for (int a = 2; a < MB - 2; ++a) {                                       \
+                _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) MF16(a, nt, fa[a & 3], fb[nt]);       \
+                SB(); fa[a & 3] = a + 4 < MB ? LD16(pa_ + (a + 4) * 1024) : LD16(pan_ + (a + 4 - MB) * 1024); \
+                SB();                                                                                  \
+            }                                                                                          \
+            _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                                         \
+                MF16(MB - 2, nt, fa[2], fb[nt]); MF16(MB - 1, nt, fa[3], fb[nt]);                      \
+                SB(); fb[nt] = LD16(pbn_ + nt * 1024); SB();                                                 \
+            }                                                                                          \
+            fa[2] = LD16(pan_ + 2 * 1024); fa[3] = LD16(pan_ + 3 * 1024); SB();                        \
+        } else {                                                                                       \
+            _Pragma("unroll") for (int a = 0; a < HB; ++a) MF16(a, 0, fa[a], fb[0]);                   \
+            SB(); _Pragma("unroll") for (int a = 0; a < HB; ++a) MF16(a, 1, fa[a], fb[1]);             \
+            SB(); fb[0] = LD16(pb_ + 2 * 1024); fb[1] = LD16(pb_ + 3 * 1024); SB();                          \
+            _Pragma("unroll") for (int a = 0; a < HB; ++a) MF16(a, 3, fa[a], fb[1]);                   \
+            SB();                                                                                      \
+            _Pragma("unroll") for (int a = 0; a < HB; ++a) { MF16(a, 2, fa[a], fb[0]); SB(); fa[a] = LD16(pa_ + (HB + a) * 1024); SB(); } \
+            _Pragma("unroll") for (int a = 0; a < HB; ++a) MF16(HB + a, 2, fa[a], fb[0]);              \
+            SB(); fb[0] = LD16(pb_); SB();                                                                   \
+            _Pragma("unroll") for (int a = 0; a < HB; ++a) MF16(HB + a, 3, fa[a], fb[1]);              \
+            SB(); fb[1] = LD16(pb_ + 1024); SB();                                                            \
+            _Pragma("unroll") for (int a = 0; a < HB; ++a) MF16(HB + a, 0, fa[a], fb[0]);              \
+            SB(); fb[0] = LD16(pbn_); SB();                                                                  \
+            _Pragma("unroll") for (int a = 0; a < HB; ++a) { MF16(HB + a, 1, fa[a], fb[1]); SB(); fa[a] = LD16(pan_ + a * 1024); SB(); } \
+            fb[1] = LD16(pbn_ + 1024); SB();                                                           \
+        }                                                                                              \
+        cur_a = __builtin_amdgcn_readfirstlane(fa_off); cur_b = __builtin_amdgcn_readfirstlane(fb_off); \
+        ADVANCE_READ();                                                                                \
+    } while (0)
+
+#pragma unroll
+    for (int s_ = 0; s_ < (NA > NB ? NA : NB) - 1; ++s_) {
+        if (s_ < NA - 1) ISSUE_A();
+        if (s_ < NB - 1) ISSUE_B();
+    }
+    WAITVM(kPrologueWait);
+    BARRIER();
+#pragma unroll
+    for (int a = 0; a < NFA; ++a) fa[a] = LD16(lds + a_adr0 + a * 1024);
+#pragma unroll
+    for (int nt = 0; nt < NFB; ++nt) fb[nt] = LD16(lds + b_adr0 + nt * 1024);
+    ADVANCE_READ();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    BARRIER();
+    if (grp == 0) {
+        for (int g = 0; g < total; ++g) {
+            COMPUTE16();
+            BARRIER();
+            ISSUE_BOTH();
+            WAIT_ITER(g);
+            BARRIER();
+        }
+    } else {
+        for (int g = 0; g < total; ++g) {
+            ISSUE_BOTH();
+            __builtin_amdgcn_sched_barrier(0);
+            BARRIER();
+            COMPUTE16();
+            WAIT_ITER(g);
+            BARRIER();
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    float keep = 0.f;
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) keep += acc[mb][nt][r];
+    if (keep == 1.2345e-30f) sink[0] = keep;
+    if (threadIdx.x == 0 && blockIdx.x == 0) reinterpret_cast<long long *>(sink)[1] = clock64() - t_start;
+}
+#undef lane_off
+
+template <int ROWS, int SHARE, int NA, int NB, int SCHED = -1>                 // SCHED -1: 32x32x16 (k), 0 / 1: 16x16x32 (k16)
 void run(const char *X, int64_t n_rows, const char *Q, float *sink, const char *what) {
-    auto kern = k<ROWS, SHARE, NA, NB>;
+    auto pick = [] { if constexpr (SCHED < 0) return k<ROWS, SHARE, NA, NB>; else return k16<ROWS, SHARE, NA, NB, SCHED>; };
+    auto kern = pick();
     constexpr int lds_bytes = NA * ROWS * 64 + NB * 16384;
     hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     const int64_t n_tiles = n_rows / ROWS;
@@ -255,16 +410,24 @@ int main() {
         hipDeviceSynchronize();
         for (int round = 0; round < 3; ++round) {
             run<256, 1, 5, 4>(X, n_rows, Q, sink, "256 x 256 (pp3: 144 KiB rings + 16 KiB records)");
+            run<256, 1, 5, 4, 0>(X, n_rows, Q, sink, "256 x 256 16x16x32, query side held");
+            run<256, 1, 5, 4, 1>(X, n_rows, Q, sink, "256 x 256 16x16x32, quarters in snake order");
             run<384, 1, 4, 3>(X, n_rows, Q, sink, "384 x 256 (144 KiB rings + 16 KiB records)");
+            run<384, 1, 4, 3, 0>(X, n_rows, Q, sink, "384 x 256 16x16x32, query side held");
+            run<384, 1, 4, 3, 1>(X, n_rows, Q, sink, "384 x 256 16x16x32, quarters in snake order");
             run<384, 1, 4, 4>(X, n_rows, Q, sink, "384 x 256 (160 KiB rings, no room for records)");
         }
         for (int round = 0; round < 2; ++round) {
             run<256, 2, 5, 4>(X, n_rows, Q, sink, "256 x 256 (pp3: 144 KiB rings + 16 KiB records)");
             run<384, 2, 4, 3>(X, n_rows, Q, sink, "384 x 256 (144 KiB rings + 16 KiB records)");
         }
-        for (int round = 0; round < 2; ++round) {
+        for (int round = 0; round < 4; ++round) {
             run<256, 4, 5, 4>(X, n_rows, Q, sink, "256 x 256 (pp3: 144 KiB rings + 16 KiB records)");
+            run<256, 4, 5, 4, 0>(X, n_rows, Q, sink, "256 x 256 16x16x32, query side held");
+            run<256, 4, 5, 4, 1>(X, n_rows, Q, sink, "256 x 256 16x16x32, quarters in snake order");
             run<384, 4, 4, 3>(X, n_rows, Q, sink, "384 x 256 (144 KiB rings + 16 KiB records)");
+            run<384, 4, 4, 3, 0>(X, n_rows, Q, sink, "384 x 256 16x16x32, query side held");
+            run<384, 4, 4, 3, 1>(X, n_rows, Q, sink, "384 x 256 16x16x32, quarters in snake order");
             run<384, 4, 4, 4>(X, n_rows, Q, sink, "384 x 256 (160 KiB rings, no room for records)");
         }
     }
